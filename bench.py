@@ -18,6 +18,10 @@ resident.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 without WORLD_SIZE: starts N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the line.  `--full` adds the oracle
+check of the timed step and every further leg (roofline legs, CPU baseline, other configurations, ingest);
+`--dump-outputs DIR` writes the last timed step's results as .npy files.
 """
 from __future__ import annotations
 
@@ -264,7 +268,17 @@ def parse():
                     help="N > 1: an exchange (all-gather + merge) that has not completed after this many seconds aborts the run "
                          "with a one-line diagnosis and exit status 3")
     ap.add_argument("--extra-json", default=None, help="where the full result object goes (default: bench_extra.json beside this file)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the oracle check of the timed step, the telemetry window, "
+                         "the HBM / Q=256 / L2 / C-ABI / boundary legs, the CPU baseline, config 2, PQ, ingest and the non-uniform "
+                         "corpora (each still subject to its --no-* option); a plain run sets up, warms up, times and reports")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the merged top-k of the last timed step as DIR/scores.npy (float32), DIR/rows.npy and "
+                         "DIR/counts.npy (float64)")
+    a = ap.parse_args()
+    if a.dump_outputs and (a.via_c_abi or a.only_distribution or a.only_pq or a.only_config2):
+        ap.error("--dump-outputs writes the headline loop's results: not with --via-c-abi or --only-*")
+    return a
 
 
 def self_launch(a) -> int:
@@ -1736,9 +1750,19 @@ def main():
     r_timed = res["rows"].cpu().numpy().copy()
     s_timed = res["scores"].cpu().numpy().copy()
     c_timed = res["counts"].cpu().numpy().copy()
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives (the merged top-k is the same on every rank); beyond 64 MB an evenly
+        # spaced, fixed subset of the queries is written
+        q_keep = min(nq, (64 << 20) // (k * 12 + 8))
+        qs = np.linspace(0, nq - 1, q_keep).round().astype(np.int64) if q_keep < nq else slice(None)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr, dt_ in (("scores", s_timed, np.float32), ("rows", r_timed, np.float64), ("counts", c_timed, np.float64)):
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr[qs].astype(dt_))
 
-    # ---- the timed configuration against the oracle over the whole resident corpus ----------------
-    if a.oracle_queries is not None:
+    # ---- the timed configuration against the oracle over the whole resident corpus (--full) -------
+    if not a.full:
+        n_oq = 0
+    elif a.oracle_queries is not None:
         n_oq = a.oracle_queries
     elif world > 1:
         n_oq = 16
@@ -1788,7 +1812,7 @@ def main():
 
     # ---- clock / power / THROTTLE REASON while the same steps run for ~1.5 s (outside the timed region) ----
     telemetry = None
-    if world == 1 and not a.no_telemetry:
+    if world == 1 and a.full and not a.no_telemetry:
         try:
             from yams_amd import telemetry as ytel
             bus = ytel.hip_pci_bus(local)
@@ -1829,7 +1853,7 @@ def main():
     stride = max(1, n_tiles // ((s_target + tr - 1) // tr))
     n_sample = (n_tiles + stride - 1) // stride
     filt_rows = min(n, (n_tiles - n_sample) * tr)
-    if world == 1 and not a.no_hbm_leg and (tb is not None or t8 is not None) and bf16 and nq >= 64:
+    if world == 1 and a.full and not a.no_hbm_leg and (tb is not None or t8 is not None) and bf16 and nq >= 64:
         q64 = 64
         s64 = torch.empty((q64, k), dtype=torch.float32, device=dev)
         r64 = torch.empty((q64, k), dtype=torch.int64, device=dev)
@@ -1874,7 +1898,7 @@ def main():
 
     # ---- the same shard at 256 queries per batch (Q in {64, 256, 1024} on config 4's shard) ----------
     q256_leg = None
-    if world == 1 and not a.no_hbm_leg and (tb is not None or t8 is not None) and bf16 and nq >= 256:
+    if world == 1 and a.full and not a.no_hbm_leg and (tb is not None or t8 is not None) and bf16 and nq >= 256:
         qm = 256
         sm = torch.empty((qm, k), dtype=torch.float32, device=dev); rm = torch.empty((qm, k), dtype=torch.int64, device=dev)
         cm = torch.empty(qm, dtype=torch.int32, device=dev)
@@ -1903,7 +1927,7 @@ def main():
     # (a prefix of the shard and of its shadows — the blocked int8 shadow of the first 10M rows is a prefix too)
     l2_leg = None
     n3 = 10_000_000
-    if (world == 1 and not a.no_l2_leg and tb is not None and t8 is not None and n >= n3 and d == 768 and nq >= 1024
+    if (world == 1 and a.full and not a.no_l2_leg and tb is not None and t8 is not None and n >= n3 and d == 768 and nq >= 1024
             and scan_flags == 0):
         view3 = acc.corpus_view(tc.data_ptr(), n3, d, row_base=row_base, rows_bf16_ptr=tb.data_ptr(), rows_nsq_ptr=tn.data_ptr(),
                                 rows_i8_ptr=t8.data_ptr(), rows_i8_meta_ptr=tm8.data_ptr())
@@ -2019,7 +2043,7 @@ def main():
 
     # ---- the same workload through the C ABI's sharded entry points (what a C++ host calls) ----------
     c_abi = None
-    if not a.no_c_abi_leg and scan_flags == 0 and t8 is not None:
+    if a.full and not a.no_c_abi_leg and scan_flags == 0 and t8 is not None:
         if world == 1:
             try:
                 c_abi = c_abi_sharded_run(a, [local], views=[view], n_query_batches=n_qb, oracle_queries=0)
@@ -2184,33 +2208,33 @@ def main():
                                       "no collective kernel waits for a CU under a persistent sweep (DESIGN 4)"}
     # CPU baseline and the ingest leg: rank 0 at N = 1 only (at N > 1 the other ranks would sit in the
     # final barrier meanwhile)
-    if not a.no_boundary_leg and world == 1:
+    if a.full and not a.no_boundary_leg and world == 1:
         try:
             free_b, _ = torch.cuda.mem_get_info()
             need = n * d * 7 * 1.15                      # the plugin's own mirror of the shard: fp32 + bf16 + int8
             out["boundary"] = boundary_leg(a, acc, torch, dev, tc, n if free_b > need + (8 << 30) else 0)
         except Exception as e:          # noqa: BLE001
             out["boundary"] = {"error": repr(e)}
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_scan(tc, tq, n, k)
-    if not a.no_distribution_legs and world == 1 and n >= 1_000_000:
+    if a.full and not a.no_distribution_legs and world == 1 and n >= 1_000_000:
         # the same shape on corpora that are not uniform on the sphere (after the headline's tensors are gone: each leg builds
         # a shard of its own)
         pending_distributions = [kd for kd in (a.distribution or "clustered,anisotropic,gaussian").split(",") if kd]
     else:
         pending_distributions = []
-    if not a.no_config2_leg and world == 1:
+    if a.full and not a.no_config2_leg and world == 1:
         try:
             sweep = [int(x) for x in a.config2_lane_sweep.split(",")] if a.config2_lane_sweep else None
             out["config2"] = config2_leg(a, torch, dev, local, lane_counts=sweep, batches=a.config2_batches)
         except Exception as e:          # noqa: BLE001 - the headline number above stands on its own
             out["config2"] = {"error": repr(e)}
-    if not a.no_pq_leg and world == 1:
+    if a.full and not a.no_pq_leg and world == 1:
         try:
             out["pq"] = pq_leg(a, torch, dev, local)
         except Exception as e:          # noqa: BLE001 - the headline number above stands on its own
             out["pq"] = {"error": repr(e)}
-    if not a.no_ingest and world == 1:
+    if a.full and not a.no_ingest and world == 1:
         del tc, tb, tn, t8, tm8, view, pipe, res
         acc.L.yams_accel_ctx_destroy(acc.ctx)   # drop the scan workspace before the ingest leg
         acc.ctx = None

@@ -9,7 +9,7 @@ python bench.py --only-config2 > $O/c2.json 2> $O/c2.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06_tau/c2.json').read().strip().splitlines()[-1]); print('config2', d.get('ms_per_step'), d.get('qps'), d.get('results_identical_to_the_oracle_run'))
 PY
-python bench.py --steps 20 --warmup 5 --no-ingest --no-cpu-baseline --no-config2-leg --no-distribution-legs --no-c-abi-leg --no-boundary-leg --no-l2-leg --no-hbm-leg --oracle-queries 64 > $O/head.json 2> $O/head.err; python - <<'PY'
+python bench.py --full --steps 20 --warmup 5 --no-ingest --no-cpu-baseline --no-config2-leg --no-distribution-legs --no-c-abi-leg --no-boundary-leg --no-l2-leg --no-hbm-leg --oracle-queries 64 > $O/head.json 2> $O/head.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06_tau/head.json').read().strip().splitlines()[-1]); print('headline', d['ms_per_step'], d['value'], d['roofline']['launch_ms'], d['roofline']['frac'], d.get('bit_exact_vs_oracle'))
 PY

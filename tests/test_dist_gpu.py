@@ -43,7 +43,7 @@ def test_bench_self_launches_n_ranks_and_checks_the_merge_against_the_oracle(tmp
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-device", "--dist-backend", "gloo",
            "--rows-per-gpu", "300000", "--dim", "256", "--queries", "300", "--k", "50", "--steps", "3", "--warmup", "1",
-           "--no-ingest", "--no-cpu-baseline", "--oracle-queries", "3", "--extra-json", str(tmp_path / "extra.json")]
+           "--full", "--no-ingest", "--no-cpu-baseline", "--oracle-queries", "3", "--extra-json", str(tmp_path / "extra.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
