@@ -186,7 +186,9 @@ public:
     }
     // The exact arm of document-level selection (sqlite_vec_backend.cpp:1508-1518: all matching rows,
     // then the best row per document, :86-125) — what the product's PQ engine falls back to whenever
-    // its compressed state is missing, stale or bypassed by a filter.
+    // its compressed state is missing, stale or bypassed by a filter.  The reduction runs on the device
+    // (AccelVectorTable::searchDocuments: k records come back, not every matching row); a plugin that cannot
+    // serve it (a corpus on several devices) gets the all-rows route below — same results, same diagnostics.
     Result<std::vector<VectorRecord>>
     searchDocumentCandidatesWithDiagnostics(const std::vector<float>& query_embedding, size_t k, float similarity_threshold,
                                             const std::unordered_set<std::string>& candidate_hashes,
@@ -194,6 +196,12 @@ public:
         resetKeepingCollectFlag(diagnostics);
         if (candidate_hashes.empty())
             return Error{ErrorCode::InvalidArgument, "Document candidate search requires candidate hashes"};
+        auto docs = withSyncedMirror([&]() -> Result<std::vector<VectorRecord>> {
+            if (query_embedding.empty()) return std::vector<VectorRecord>{};
+            return table_.searchDocuments(query_embedding, k, similarity_threshold, candidate_hashes, &diagnostics);
+        });
+        if (docs || docs.error().code != ErrorCode::NotImplemented) return docs;
+        resetKeepingCollectFlag(diagnostics);
         auto rows = search(query_embedding, 0, similarity_threshold, std::nullopt, candidate_hashes, {}, &diagnostics,
                            ExactRowSelection::AllMatching);
         if (!rows) return rows;
@@ -429,7 +437,8 @@ private:
         if (auto s = table_.sync(); !s) return s.error();
         return scan();
     }
-    // retainBestRecordPerDocument, sqlite_vec_backend.cpp:86-125
+public:
+    // retainBestRecordPerDocument, sqlite_vec_backend.cpp:86-125 (public: the all-rows route, for parity checks)
     static std::vector<VectorRecord> bestRecordPerDocument(std::vector<VectorRecord> records, size_t limit) {
         std::unordered_map<std::string, VectorRecord> best;
         for (auto& r : records) {
@@ -450,6 +459,7 @@ private:
         if (records.size() > limit) records.resize(limit);
         return records;
     }
+private:
 
     std::shared_ptr<accel::Plugin> plugin_;
     std::shared_ptr<IVectorStore> durable_;

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <numeric>
 #include <optional>
 #include <string>
@@ -89,8 +90,8 @@ struct L2Setting {
 class AccelVectorIndex {
 public:
     AccelVectorIndex(std::shared_ptr<accel::Plugin> plugin, yams_vector_scan_v1* vt, size_t embeddingDim,
-                     VectorSearchEngine engine = VectorSearchEngine::ExactScan)
-        : plugin_(std::move(plugin)), vt_(vt), dim_(embeddingDim), engine_(engine) {}
+                     VectorSearchEngine engine = VectorSearchEngine::ExactScan, yams_vector_doc_scan_v1* docVt = nullptr)
+        : plugin_(std::move(plugin)), vt_(vt), docVt_(docVt), dim_(embeddingDim), engine_(engine) {}
     ~AccelVectorIndex() { if (corpus_) vt_->corpus_destroy(vt_->self, corpus_); }
 
     Result<void> initialize() {
@@ -125,6 +126,7 @@ public:
             byId_[r.chunk_id] = records_.size();
             byDoc_[r.document_hash].push_back(static_cast<uint32_t>(records_.size()));
             records_.push_back(r);
+            docsDirty_ = true;
             alive_.push_back(1);
             zeroNorm_.push_back(isZeroNorm(r.embedding) ? 1 : 0);
         }
@@ -241,6 +243,67 @@ public:
         if (!r) return r.error();
         return std::move(r.value().front());
     }
+    // Document-level selection (CandidateFilterMode::DocumentTopK) on the device: the exact arm of
+    // sqlite_vec_backend.cpp:1508-1518 — every matching row of the candidate documents, then the best row per document
+    // (retainBestRecordPerDocument, :86-125) — with the reduction next to the fp64 score (vector_doc_scan_v1.search_docs).
+    // Only the k winners become records.  Results and diagnostics are those of searchSimilar(AllMatching) followed by
+    // that reduction.  ErrorCode::NotImplemented when the plugin cannot serve it (no vector_doc_scan_v1, a corpus on
+    // several devices, the vec0 L2 engine): the caller keeps the all-rows route.
+    Result<std::vector<VectorRecord>> searchDocuments(const std::vector<float>& query, size_t k, float similarityThreshold,
+                                                      const std::unordered_set<std::string>& candidate_hashes,
+                                                      VectorSearchDiagnostics* diagnostics = nullptr) {
+        if (!initialized_) return Error{ErrorCode::NotInitialized, "Database not initialized"};
+        if (!docVt_ || engine_ == VectorSearchEngine::Vec0L2 || k > YAMS_SCAN_MAX_K)
+            return Error{ErrorCode::NotImplemented, "document search not served"};
+        if (query.size() != dim_)
+            return Error{ErrorCode::InvalidArgument, "Query embedding dimension mismatch (expected=" + std::to_string(dim_) +
+                                                         ", got=" + std::to_string(query.size()) + ")"};
+        if (auto sy = syncMirror(); !sy) return sy.error();
+        if (auto sd = syncDocuments(); !sd) return sd.error();
+        // the candidate mask exactly as searchSimilar builds it (tombstones excluded)
+        std::vector<uint32_t> mask((records_.size() + 31) / 32, 0u);
+        size_t visited = 0;
+        auto consider = [&](size_t r) {
+            if (!alive_[r]) return;
+            ++visited;
+            mask[r >> 5] |= 1u << (r & 31);
+        };
+        if (!candidate_hashes.empty()) {
+            for (const auto& h : candidate_hashes)
+                if (auto it = byDoc_.find(h); it != byDoc_.end())
+                    for (uint32_t r : it->second) consider(r);
+        } else {
+            for (size_t r = 0; r < records_.size(); ++r) consider(r);
+        }
+        if (mask.empty()) mask.push_back(0u);
+        // (the all-rows route collects the visited hashes when its rows fit one device call, :4189-4197)
+        if (diagnostics && diagnostics->collectVisitedDocumentHashes && std::max<size_t>(visited, 1) <= YAMS_SCAN_MAX_K)
+            for (size_t r = 0; r < records_.size(); ++r)
+                if ((mask[r >> 5] >> (r & 31)) & 1u) diagnostics->visitedDocumentHashes.insert(records_[r].document_hash);
+        const uint32_t kk = static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(k, 1), YAMS_SCAN_MAX_K)); // (k = 0 still validates)
+        yams_scan_hit_t* hits = nullptr; uint32_t* counts = nullptr; uint64_t matching = 0; yams_scan_diag_t diag{};
+        const yams_status_t st = docVt_->search_docs(docVt_->self, corpus_, query.data(), 1, static_cast<uint32_t>(dim_), kk,
+                                                     similarityThreshold, mask.data(), &hits, &counts, &matching, &diag);
+        if (st == YAMS_ERR_INVALID_ARG)
+            return Error{ErrorCode::InvalidArgument, "Exact vector search requires a finite, non-zero query embedding"};
+        if (st != YAMS_OK) return Error{accel::mapStatus(st), "document search failed"};
+        std::vector<VectorRecord> out;
+        for (uint32_t i = 0; i < counts[0] && i < k; ++i) {
+            VectorRecord rec = records_[static_cast<size_t>(hits[i].row)];
+            rec.relevance_score = hits[i].similarity;
+            rec.embedding_dim = dim_;
+            out.push_back(std::move(rec));
+        }
+        docVt_->free_doc_hits(docVt_->self, hits, counts);
+        if (diagnostics) {
+            diagnostics->usedExactScan = true; diagnostics->rowsVisitedObserved = true;
+            diagnostics->exactDistanceEvaluationsObserved = true;
+            diagnostics->rowsVisited += visited;
+            diagnostics->exactDistanceEvaluations += visited;
+            diagnostics->returnedRows = static_cast<size_t>(matching);   // matching rows, before the reduction
+        }
+        return out;
+    }
     // Every live record, in mirror order (retrieval methods of a backend built on this index).
     template <typename Fn> void forEachRecord(Fn&& fn) const {
         for (size_t r = 0; r < records_.size(); ++r) if (alive_[r]) fn(records_[r]);
@@ -351,6 +414,7 @@ private:
             }
             if (vt_->corpus_clear(vt_->self, corpus_) != YAMS_OK) return Error{ErrorCode::InternalError, "corpus_clear failed"};
             deviceRows_ = 0;
+            docsDirty_ = true;
             ranksDirty_ = true;
         }
         const bool appended = records_.size() > deviceRows_;
@@ -369,6 +433,26 @@ private:
                 return Error{ErrorCode::InternalError, "corpus_set_tie_ranks failed"};
         }
         ranksDirty_ = false;
+        return {};
+    }
+
+    // The row -> document map of the mirror, uploaded before the first document search after a change (the other
+    // search paths never look at it).  Ordinals follow byDoc_; doc_rank = the hash's rank in std::string (byte) order.
+    Result<void> syncDocuments() {
+        std::lock_guard<std::mutex> lk(docMu_);   // (document searches of a host share its lock: one of them uploads)
+        if (!docsDirty_ && docRows_ == records_.size()) return {};
+        std::vector<const std::string*> hashes;
+        for (const auto& [h, rows] : byDoc_) if (!h.empty()) hashes.push_back(&h);
+        std::sort(hashes.begin(), hashes.end(), [](const std::string* a, const std::string* b) { return *a < *b; });
+        std::vector<uint32_t> rowDoc(records_.size(), YAMS_SCAN_NO_DOC), rank(hashes.size());
+        for (uint32_t d = 0; d < hashes.size(); ++d) {
+            rank[d] = d;   // (ordinals are assigned in hash order: the rank of ordinal d is d)
+            for (uint32_t r : byDoc_.at(*hashes[d])) rowDoc[r] = d;
+        }
+        const yams_status_t st = docVt_->corpus_set_documents(docVt_->self, corpus_, rowDoc.data(), rowDoc.size(), rank.data(),
+                                                              static_cast<uint32_t>(hashes.size()));
+        if (st != YAMS_OK) return Error{accel::mapStatus(st), "corpus_set_documents failed"};
+        docsDirty_ = false; docRows_ = records_.size();
         return {};
     }
 
@@ -583,6 +667,10 @@ public:
 private:
     std::shared_ptr<accel::Plugin> plugin_;
     yams_vector_scan_v1* vt_;
+    yams_vector_doc_scan_v1* docVt_ = nullptr;   // nullable: a plugin without vector_doc_scan_v1
+    std::mutex docMu_;
+    bool docsDirty_ = true;
+    size_t docRows_ = 0;
     size_t dim_;
     VectorSearchEngine engine_;
     L2Setting l2_;
@@ -603,7 +691,8 @@ inline Result<std::unique_ptr<AccelVectorIndex>> createAccelVectorIndex(std::sha
                                                                         VectorSearchEngine engine = VectorSearchEngine::ExactScan) {
     auto vt = plugin->getInterface<yams_vector_scan_v1>(YAMS_IFACE_VECTOR_SCAN_V1, YAMS_IFACE_VECTOR_SCAN_V1_VERSION);
     if (!vt) return vt.error();
-    return std::make_unique<AccelVectorIndex>(std::move(plugin), vt.value(), dim, engine);
+    auto docVt = plugin->getInterface<yams_vector_doc_scan_v1>(YAMS_IFACE_VECTOR_DOC_SCAN_V1, YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION);
+    return std::make_unique<AccelVectorIndex>(std::move(plugin), vt.value(), dim, engine, docVt ? docVt.value() : nullptr);
 }
 
 // The `vectors` table holds rows of ANY dimension; a search only sees the rows whose embedding_dim
@@ -709,6 +798,15 @@ public:
         if (it == byDim_.end()) return searchSimilar(query, selection == ExactRowSelection::AllMatching ? 1 : k,
                                                      similarityThreshold, std::nullopt, candidate_hashes, {}, diagnostics);
         return it->second->searchSimilar(query, k, similarityThreshold, std::nullopt, candidate_hashes, {}, diagnostics, selection);
+    }
+    // Document-level selection of the query's dimension (AccelVectorIndex::searchDocuments); NotImplemented when no
+    // mirror of that dimension exists or the plugin cannot serve it (the caller keeps the all-rows route).
+    Result<std::vector<VectorRecord>> searchDocuments(const std::vector<float>& query, size_t k, float similarityThreshold,
+                                                      const std::unordered_set<std::string>& candidate_hashes,
+                                                      VectorSearchDiagnostics* diagnostics = nullptr) {
+        auto it = byDim_.find(query.size());
+        if (it == byDim_.end()) return Error{ErrorCode::NotImplemented, "no mirror of this dimension"};
+        return it->second->searchDocuments(query, k, similarityThreshold, candidate_hashes, diagnostics);
     }
     template <typename Fn> void forEachRecord(Fn&& fn) const {
         for (const auto& [dim, idx] : byDim_) idx->forEachRecord(fn);

@@ -28,6 +28,8 @@
  *   yams_cdc_chunk_*          RabinChunker::chunkDataLazy (src/chunking/rabin_chunker.cpp:63-152)
  *                             and StreamingChunker::chunkData (include/yams/chunking/
  *                             streaming_chunker.h:146-204, src/chunking/streaming_chunker.cpp:37-137).
+ *   yams_scan_doc_topk_*      the exact arm of document-level selection, sqlite_vec_backend.cpp:1508-1518 + :86-125
+ *                             (retainBestRecordPerDocument), with the reduction on the device.
  *   yams_ingest_*             the hash + chunk_file phases of ContentStore::store,
  *                             src/api/content_store_impl.cpp:199-231 (caller contract only).
  *
@@ -532,8 +534,9 @@ YAMS_ACCEL_API yams_status_t yams_synth_bytes_device(yams_accel_ctx* ctx, uint64
  *   3. re-scores them with VectorDatabase::computeCosineSimilarity(raw query, row) in fp64, the reference's summation
  *      order (:4023-4034), drops similarity < threshold (:4036-4038);
  *   4. sorts by (similarity desc, chunk_id asc) and cuts to k (:4041-4051).
- * `exact_fallback` indexes (:3882-3893) are the host's call to yams_scan_topk_device.  DocumentTopK selection
- * (retainBestRecordPerDocument) stays on the host: ask for k = the candidate count. */
+ * `exact_fallback` indexes (:3882-3893) are the host's call to yams_scan_topk_device.  PQ's own DocumentTopK selection
+ * (approxK = the candidate count, then retainBestRecordPerDocument) stays on the host; the exact arm of document-level
+ * selection is yams_scan_doc_topk_device. */
 typedef struct yams_scan_pq_index_s {
     const uint8_t* codes;       /* device [n_codes][m], 4-byte aligned: code of indexed row i = bytes [i * m, (i + 1) * m)          */
     uint64_t n_codes;           /* indexed rows (SimeonPqIndexState::rowids.size()), < 2^32                                        */
@@ -572,6 +575,50 @@ YAMS_ACCEL_API yams_status_t yams_scan_pq_topk_device(yams_accel_ctx* ctx, const
                                                       uint32_t n_queries, const yams_scan_pq_params_t* params,
                                                       const uint32_t* candidates, uint64_t n_candidates, float* out_scores,
                                                       int64_t* out_rows, uint32_t* out_counts, yams_scan_diag_t* diag);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Document-level top-k: the k best documents, each shown by its best row                      */
+/* ------------------------------------------------------------------------------------------ */
+/* CandidateFilterMode::DocumentTopK (include/yams/vector/vector_types.h:205-216): VectorDatabase sends it to
+ * IDocumentCandidateVectorStore::searchDocumentCandidatesWithDiagnostics (vector_database.cpp:553-567), whose exact arm
+ * is "every matching row of the candidate documents, then retainBestRecordPerDocument"
+ * (sqlite_vec_backend.cpp:1508-1518, :86-125).  Here the per-document reduction happens on the device, next to the fp64
+ * score that decides it: every allowed row is read once per group of queries, and k documents come back. */
+#define YAMS_SCAN_NO_DOC 0xffffffffu
+typedef struct yams_scan_docs_s {
+    const uint32_t* row_doc;  /* device [n_rows]: document ordinal of each row; YAMS_SCAN_NO_DOC = the row has no
+                                 document_hash: scored and counted, never returned (:91-93)                     */
+    const uint32_t* doc_rank; /* device [n_docs], nullable: rank of the document's hash in byte-wise (memcmp)
+                                 order, the cross-document tie-break; a permutation of 0 .. n_docs - 1;
+                                 NULL = ordinal order                                                           */
+    uint32_t n_docs, reserved;
+} yams_scan_docs_t;
+
+/* Per query: the best row of every document by (similarity desc, tie rank asc) (:96-105), then the best k documents by
+ * (similarity desc, doc_rank asc) (:113-121).  The rows are scored exactly as the cosine fast path scores them
+ * (:4253-4279: fp64, sequential, rows with norm^2 <= 1e-12 or a non-finite norm or score dropped, similarity < threshold
+ * dropped) — bit for bit what yams_scan_topk_device returns for the same row.
+ *   out_scores    device [n_queries][k] fp32, best first; unused slots hold -inf
+ *   out_rows      device [n_queries][k] int64: row_base + row ordinal of the document's best row; unused -1
+ *   out_docs      device [n_queries][k] uint32, nullable: document ordinal; unused YAMS_SCAN_NO_DOC
+ *   out_counts    device [n_queries] uint32: documents returned
+ *   out_matching  device [n_queries] uint64, nullable: rows >= threshold, before the reduction (the reference's
+ *                 returnedRows of this path; diag->returned_rows is their sum)
+ * As yams_scan_topk_device: query validation (a non-finite query or norm^2 < 1e-10 fails the whole batch with
+ * YAMS_ERR_INVALID_ARG), k == 0 gives an empty result, k <= YAMS_SCAN_MAX_K, row_mask / tie_rank / rank_row / row_base.
+ * Cosine only: YAMS_SCAN_L2, YAMS_SCAN_FLAG_RECORD_PATH and every flag but the filter-choice bits give
+ * YAMS_ERR_UNSUPPORTED (DocumentTopK carries no metadata filters, :1571-1575), as does a striped shard.  The filter
+ * shadows are ignored: every allowed row is scored in fp64, the reference's own cost model for this mode.
+ * Diagnostics: used_exact_scan = 1, path = 1, rows_visited = exact_distance_evaluations = allowed rows per query.
+ * A row_doc entry >= n_docs (other than YAMS_SCAN_NO_DOC) or a doc_rank that is not a permutation: YAMS_ERR_INVALID_ARG.
+ * Any batch size: the per-document keys (16 bytes per query and document) are processed in slices of queries that
+ * keep them within 256 MiB.  The call synchronises the context's stream before returning. */
+YAMS_ACCEL_API yams_status_t yams_scan_doc_topk_device(
+    yams_accel_ctx* ctx, const yams_scan_corpus_t* corpus, const yams_scan_docs_t* docs,
+    const float* queries, uint32_t n_queries, const yams_scan_params_t* params,
+    float* out_scores, int64_t* out_rows, uint32_t* out_docs, uint32_t* out_counts,
+    uint64_t* out_matching /* nullable [n_queries]: rows >= threshold, before the reduction */,
+    yams_scan_diag_t* diag);
 
 /* ------------------------------------------------------------------------------------------ */
 /* SHA-256                                                                                      */
@@ -849,6 +896,29 @@ typedef struct yams_vector_scan_v1 {
                                const uint32_t* candidates, uint64_t n_candidates, yams_scan_hit_t** out_hits,
                                uint32_t** out_counts, yams_scan_diag_t* out_diag);
 } yams_vector_scan_v1;
+
+/* Document-level selection over a vector_scan_v1 corpus (yams_scan_doc_topk_device).  A separate interface, version 1,
+ * so that vector_scan_v1 keeps its version: it is served by yams_plugin_get_interface but NOT listed in the manifest
+ * (the reference's loader does not consult the manifest in getInterface, abi_plugin_loader.cpp:657-681; adding it there
+ * is a separate change).  The corpus ids are vector_scan_v1's. */
+#define YAMS_IFACE_VECTOR_DOC_SCAN_V1 "vector_doc_scan_v1"
+#define YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION 1u
+typedef struct yams_vector_doc_scan_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION */
+    void* self;
+    /* The row -> document map of a corpus (host arrays): row_doc [n_rows] (n_rows == the corpus's rows;
+     * YAMS_SCAN_NO_DOC = no document), doc_rank [n_docs] nullable (see yams_scan_docs_t).  Replaces the previous map;
+     * rows appended later are YAMS_SCAN_NO_DOC until it is called again; corpus_clear drops it. */
+    yams_status_t (*corpus_set_documents)(void* self, uint64_t corpus_id, const uint32_t* row_doc, uint64_t n_rows,
+                                          const uint32_t* doc_rank, uint32_t n_docs);
+    /* k documents per query, row_mask (host, nullable) as search_batch_masked: hits [n_queries][k] with
+     * distance = 1 - similarity, counts [n_queries], out_matching (host [n_queries], nullable) = rows >= threshold
+     * before the reduction.  Release with free_doc_hits.  A corpus dealt to several devices: YAMS_ERR_UNSUPPORTED. */
+    yams_status_t (*search_docs)(void* self, uint64_t corpus_id, const float* queries, uint32_t n_queries, uint32_t dim,
+                                 uint32_t k, float similarity_threshold, const uint32_t* row_mask, yams_scan_hit_t** out_hits,
+                                 uint32_t** out_counts, uint64_t* out_matching, yams_scan_diag_t* out_diag);
+    void (*free_doc_hits)(void* self, yams_scan_hit_t* hits, uint32_t* counts);
+} yams_vector_doc_scan_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

@@ -78,6 +78,13 @@ class ScanPqIndex(C.Structure):     # yams_scan_pq_index_t
                 ("tie_rank", vp), ("key_row", vp)]
 
 
+class ScanDocs(C.Structure):        # yams_scan_docs_t
+    _fields_ = [("row_doc", vp), ("doc_rank", vp), ("n_docs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+NO_DOC = 0xFFFFFFFF                 # YAMS_SCAN_NO_DOC
+
+
 class ScanPqParams(C.Structure):    # yams_scan_pq_params_t
     _fields_ = [("k", C.c_uint32), ("similarity_threshold", C.c_float), ("rerank_factor", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -152,6 +159,16 @@ class VectorScanV1(C.Structure):
     ]
 
 
+class VectorDocScanV1(C.Structure):  # vector_doc_scan_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("corpus_set_documents", C.CFUNCTYPE(ST, vp, C.c_uint64, u32p, C.c_uint64, u32p, C.c_uint32)),
+        ("search_docs", C.CFUNCTYPE(ST, vp, C.c_uint64, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, u32p,
+                                    C.POINTER(C.POINTER(ScanHit)), C.POINTER(u32p), u64p, C.POINTER(ScanDiag))),
+        ("free_doc_hits", C.CFUNCTYPE(None, vp, C.POINTER(ScanHit), u32p)),
+    ]
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -205,6 +222,7 @@ EXPORTS = [
     "yams_accel_download", "yams_accel_last_kernel_ms", "yams_accel_enable_kernel_timing",
     "yams_accel_debug_fail_alloc_after", "yams_accel_debug_alloc_faults", "yams_accel_debug_alloc_injection_compiled",
     "yams_scan_topk_device", "yams_scan_topk_host", "yams_scan_merge_topk_device", "yams_scan_pq_topk_device",
+    "yams_scan_doc_topk_device",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -287,6 +305,8 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
                                         C.POINTER(ScanDiag)]
     L.yams_scan_pq_topk_device.argtypes = [vp, C.POINTER(ScanCorpus), C.POINTER(ScanPqIndex), vp, vp, C.c_uint32, C.POINTER(ScanPqParams),
                                            vp, C.c_uint64, vp, vp, vp, C.POINTER(ScanDiag)]
+    L.yams_scan_doc_topk_device.argtypes = [vp, C.POINTER(ScanCorpus), C.POINTER(ScanDocs), vp, C.c_uint32, C.POINTER(ScanParams),
+                                            vp, vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (AccelError, CdcConfig, IngestResult, ScanCorpus, ScanDiag, ScanParams,
+from ._lib import (AccelError, CdcConfig, IngestResult, ScanCorpus, ScanDiag, ScanDocs, ScanParams,
                    CDC_RABIN, CDC_STREAMING, SCAN_COSINE, SCAN_L2)
 
 DEFAULT_POLY = 0x3DA3358B4DC173
@@ -401,6 +401,43 @@ class Accel:
                                                counts.ctypes.data, dist.ctypes.data,
                                                C.byref(diag)))
         return ScanResult(scores[:, :k], rows[:, :k], counts, dist[:, :k], diag.as_dict())
+
+    def docs_view(self, row_doc_ptr: int, n_docs: int, doc_rank_ptr: int | None = None) -> ScanDocs:
+        """yams_scan_docs_t over device arrays: row_doc u32 [n_rows] (NO_DOC = no document), doc_rank u32 [n_docs] or None."""
+        return ScanDocs(row_doc_ptr, doc_rank_ptr, n_docs, 0)
+
+    def scan_doc_topk(self, corpus: ScanCorpus, docs: ScanDocs, queries: np.ndarray, k: int, threshold: float = 0.0,
+                      metric: int = SCAN_COSINE, flags: int = 0) -> ScanResult:
+        """Document-level top-k (yams_scan_doc_topk_device) from host queries: the k best documents per query, each by its
+        best row.  The result's `docs` holds the document ordinals, `matching` the rows >= threshold before the reduction."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        kk = max(k, 1)
+        d_q = self.to_device(q) if q.size else None
+        d_s = self.alloc(nq * kk * 4 + 16); d_r = self.alloc(nq * kk * 8 + 16); d_d = self.alloc(nq * kk * 4 + 16)
+        d_n = self.alloc(nq * 4 + 16); d_m = self.alloc(nq * 8 + 16)
+        try:
+            prm = ScanParams(k, threshold, metric, flags)
+            diag = ScanDiag()
+            self._check(self.L.yams_scan_doc_topk_device(self.ctx, C.byref(corpus), C.byref(docs), d_q.ptr if d_q else None, nq,
+                                                         C.byref(prm), d_s.ptr, d_r.ptr, d_d.ptr, d_n.ptr, d_m.ptr, C.byref(diag)))
+            counts = d_n.download(np.uint32, nq)
+            scores = d_s.download(np.float32, nq * kk).reshape(nq, kk)[:, :k]
+            rows = d_r.download(np.int64, nq * kk).reshape(nq, kk)[:, :k]
+            docs_out = d_d.download(np.uint32, nq * kk).reshape(nq, kk)[:, :k]
+            matching = d_m.download(np.uint64, nq)
+        finally:
+            for b in (d_q, d_s, d_r, d_d, d_n, d_m):
+                if b is not None:
+                    b.free()
+        if k == 0:
+            scores = np.zeros((nq, 0), np.float32); rows = np.zeros((nq, 0), np.int64); docs_out = np.zeros((nq, 0), np.uint32)
+        r = ScanResult(scores, rows, counts, None, diag.as_dict())
+        r.docs = docs_out
+        r.matching = matching
+        return r
 
     def scan_pq_topk(self, corpus: ScanCorpus, codes: np.ndarray, luts: np.ndarray, queries: np.ndarray, k: int, threshold: float = -1.0,
                      rerank_factor: int = 2, tie_keys: np.ndarray | None = None, row_of_index: np.ndarray | None = None,

@@ -256,12 +256,27 @@ struct PqIndex {
     }
 };
 
+// The row -> document map of a corpus (vector_doc_scan_v1.corpus_set_documents), on the corpus's device.
+struct DocMap {
+    std::vector<uint32_t> row_doc;   // host copy: rows appended after the map was set are NO_DOC (padded per search)
+    uint32_t* d_row_doc = nullptr; uint32_t* d_doc_rank = nullptr;
+    uint64_t n_rows = 0; uint32_t n_docs = 0; int device = 0;
+    void release() {
+        if (d_row_doc || d_doc_rank) (void)hipSetDevice(device);
+        if (d_row_doc) (void)hipFree(d_row_doc);
+        if (d_doc_rank) (void)hipFree(d_doc_rank);
+        d_row_doc = d_doc_rank = nullptr; n_rows = 0; n_docs = 0;
+        std::vector<uint32_t>().swap(row_doc);
+    }
+};
+
 struct Corpus {
     uint32_t dim = 0;
     uint64_t n_rows = 0;
     int i8_flags = -1;               // layout of the int8 shadow (YAMS_SCAN_I8_*), decided at the first append; -1: not yet
     uint64_t i8_decided_rows = 0;    // rows the "auto" decision looked at (one taken from fewer than 4096 rows is taken again once they are there)
     PqIndex pq;                      // (version 2 of the vtable: pq_index_set / search_pq)
+    DocMap docs;                     // (vector_doc_scan_v1)
     std::vector<ShardStore> sh;      // one per plugin device
     GrowBuf rank_of_row;             // device 0: the corpus-wide chunk_id ranking (cross-shard ties)
     bool has_ranks = false;
@@ -673,6 +688,7 @@ yams_status_t vs_corpus_set_tie_ranks(void*, uint64_t id, const uint32_t* ranks,
 
 void release_corpus(Corpus& c) {
     c.pq.release();
+    c.docs.release();
     for (auto& s : c.sh) s.release();
     c.rank_of_row.release();
     c.n_rows = 0; c.has_ranks = false; c.i8_flags = -1; c.i8_decided_rows = 0;
@@ -685,6 +701,7 @@ yams_status_t vs_corpus_clear(void*, uint64_t id) {
     if (!c) return YAMS_ERR_NOT_FOUND;
     std::unique_lock<std::shared_mutex> lk(c->mu);
     for (auto& s : c->sh) { s.n_rows = 0; s.has_tie = false; }
+    c->docs.release();
     c->n_rows = 0; c->has_ranks = false; c->i8_flags = -1; c->i8_decided_rows = 0;
     return YAMS_OK;
 }
@@ -917,6 +934,118 @@ yams_vector_scan_v1 g_vector_scan = {
     GUARDED(vs_corpus_set_tie_ranks), GUARDED(vs_corpus_clear), GUARDED(vs_corpus_destroy), GUARDED(vs_corpus_size),
     GUARDED(vs_search_batch), GUARDED(vs_free_hits), GUARDED(vs_runtime_info), GUARDED(vs_free_string),
     GUARDED(vs_search_batch_masked), GUARDED(vs_search_batch_ex), GUARDED(vs_pq_index_set), GUARDED(vs_search_pq)};
+
+// ---- vector_doc_scan_v1: document-level selection over a vector_scan_v1 corpus (yams_scan_doc_topk_device) -----------------
+yams_status_t ds_corpus_set_documents(void*, uint64_t id, const uint32_t* row_doc, uint64_t n_rows, const uint32_t* doc_rank,
+                                      uint32_t n_docs) {
+    NEED_INIT();
+    auto c = find_corpus(id);
+    if (!c) return YAMS_ERR_NOT_FOUND;
+    std::unique_lock<std::shared_mutex> lk(c->mu);
+    if (c->sh.size() != 1) return YAMS_ERR_UNSUPPORTED;      // (a document map over a striped corpus: not built)
+    if (n_rows != c->n_rows || (n_rows && !row_doc) || n_docs == YAMS_SCAN_NO_DOC) return YAMS_ERR_INVALID_ARG;
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (row_doc[r] != YAMS_SCAN_NO_DOC && row_doc[r] >= n_docs) return YAMS_ERR_INVALID_ARG;
+    if (doc_rank) {
+        std::vector<uint8_t> seen(n_docs, 0);
+        for (uint32_t d = 0; d < n_docs; ++d) {
+            if (doc_rank[d] >= n_docs || seen[doc_rank[d]]) return YAMS_ERR_INVALID_ARG; // not a permutation
+            seen[doc_rank[d]] = 1;
+        }
+    }
+    c->docs.release();
+    DocMap m; m.device = c->sh[0].device; m.n_rows = n_rows; m.n_docs = n_docs;
+    m.row_doc.assign(row_doc, row_doc + n_rows);
+    (void)hipSetDevice(m.device);
+    bool ok = (n_rows == 0 || yams_accel::ya_malloc(reinterpret_cast<void**>(&m.d_row_doc), n_rows * 4) == hipSuccess) &&
+              (!doc_rank || n_docs == 0 || yams_accel::ya_malloc(reinterpret_cast<void**>(&m.d_doc_rank), static_cast<size_t>(n_docs) * 4) == hipSuccess);
+    if (!ok) { (void)hipGetLastError(); m.release(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    ok = (!m.d_row_doc || yams_accel_upload(w.v, m.d_row_doc, row_doc, n_rows * 4) == YAMS_OK) &&
+         (!m.d_doc_rank || yams_accel_upload(w.v, m.d_doc_rank, doc_rank, static_cast<size_t>(n_docs) * 4) == YAMS_OK);
+    if (!ok) { m.release(); return YAMS_ERR_INTERNAL; }
+    c->docs = std::move(m);
+    return YAMS_OK;
+}
+
+yams_status_t ds_search_docs(void*, uint64_t id, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, float threshold,
+                             const uint32_t* row_mask_host, yams_scan_hit_t** out_hits, uint32_t** out_counts,
+                             uint64_t* out_matching, yams_scan_diag_t* out_diag) {
+    NEED_INIT();
+    if (!out_hits || !out_counts) return YAMS_ERR_INVALID_ARG;
+    *out_hits = nullptr; *out_counts = nullptr;
+    if (k > YAMS_SCAN_MAX_K) return YAMS_ERR_UNSUPPORTED;
+    auto c = find_corpus(id);
+    if (!c) return YAMS_ERR_NOT_FOUND;
+    if (dim != c->dim) return YAMS_ERR_INVALID_ARG;           // (vector_database.cpp:545-550)
+    if (nq && !queries) return YAMS_ERR_INVALID_ARG;
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    if (c->sh.size() != 1) return YAMS_ERR_UNSUPPORTED;
+    const ShardStore& s = c->sh[0];
+    const DocMap& dm = c->docs;
+    const size_t slots = static_cast<size_t>(nq) * std::max<uint32_t>(k, 1);
+    auto* counts = static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)));
+    auto* hits = static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)));
+    if (!counts || !hits) { std::free(counts); std::free(hits); return YAMS_ERR_INTERNAL; }
+    auto done = [&](yams_status_t st) { if (st != YAMS_OK) { std::free(counts); std::free(hits); } else { *out_hits = hits; *out_counts = counts; } return st; };
+    for (size_t o = 0; o < slots; ++o) hits[o].row = -1;
+    if (nq == 0) { if (out_diag) std::memset(out_diag, 0, sizeof *out_diag); return done(YAMS_OK); }
+    (void)hipSetDevice(s.device);
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    yams_accel_ctx* x = w.v;
+    float* d_q; float* d_s; int64_t* d_r; uint32_t* d_n; uint64_t* d_m;
+    yams_status_t st;
+    if ((st = yams_accel::ws_get(x, "plugin_doc_queries", static_cast<size_t>(nq) * dim * 4, (void**)&d_q)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_doc_scores", slots * 4, (void**)&d_s)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_doc_rows", slots * 8, (void**)&d_r)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_doc_counts", static_cast<size_t>(nq) * 4, (void**)&d_n)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_doc_matching", static_cast<size_t>(nq) * 8, (void**)&d_m)) != YAMS_OK) return done(st);
+    if (yams_accel_upload(x, d_q, queries, static_cast<size_t>(nq) * dim * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
+    yams_scan_corpus_t v;
+    std::memset(&v, 0, sizeof v);
+    v.rows = s.rows.as<float>(); v.n_rows = s.n_rows; v.dim = c->dim;
+    if (s.has_tie) { v.tie_rank = s.tie.as<uint32_t>(); v.rank_row = s.inv.as<uint32_t>(); }
+    if (row_mask_host && s.n_rows) {   // document_hash / candidate_hashes restriction (:4137-4175)
+        const size_t words = (s.n_rows + 31) / 32;
+        std::vector<uint32_t> mask(row_mask_host, row_mask_host + words);
+        if (s.n_rows % 32) mask.back() &= (1u << (s.n_rows % 32)) - 1u;
+        uint64_t bits = 0;
+        for (uint32_t m : mask) bits += static_cast<uint64_t>(__builtin_popcount(m));
+        uint32_t* d_mask;
+        if ((st = yams_accel::ws_get(x, "plugin_doc_mask", words * 4, (void**)&d_mask)) != YAMS_OK) return done(st);
+        if (yams_accel_upload(x, d_mask, mask.data(), words * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
+        v.row_mask = d_mask; v.row_mask_count = bits;
+    }
+    // the document map; rows appended after it was set have no document
+    yams_scan_docs_t docs{dm.d_row_doc, dm.d_doc_rank, dm.n_docs, 0};
+    if (s.n_rows > dm.n_rows) {
+        std::vector<uint32_t> padded(s.n_rows, YAMS_SCAN_NO_DOC);
+        std::copy(dm.row_doc.begin(), dm.row_doc.end(), padded.begin());
+        uint32_t* d_pad;
+        if ((st = yams_accel::ws_get(x, "plugin_doc_row_doc", padded.size() * 4, (void**)&d_pad)) != YAMS_OK) return done(st);
+        if (yams_accel_upload(x, d_pad, padded.data(), padded.size() * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
+        docs.row_doc = d_pad;
+    }
+    yams_scan_params_t prm{k, threshold, YAMS_SCAN_COSINE, 0};
+    if ((st = yams_scan_doc_topk_device(x, &v, &docs, d_q, nq, &prm, d_s, d_r, nullptr, d_n, d_m, out_diag)) != YAMS_OK) return done(st);
+    std::vector<float> scores(slots); std::vector<int64_t> rows(slots);
+    if (yams_accel_download(x, counts, d_n, static_cast<size_t>(nq) * 4) != YAMS_OK ||
+        (k && yams_accel_download(x, scores.data(), d_s, slots * 4) != YAMS_OK) ||
+        (k && yams_accel_download(x, rows.data(), d_r, slots * 8) != YAMS_OK) ||
+        (out_matching && yams_accel_download(x, out_matching, d_m, static_cast<size_t>(nq) * 8) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
+    for (uint32_t q = 0; q < nq; ++q)
+        for (uint32_t i = 0; i < k && i < counts[q]; ++i) {
+            const size_t o = static_cast<size_t>(q) * k + i;
+            hits[o].row = rows[o]; hits[o].similarity = scores[o]; hits[o].distance = 1.0f - scores[o];
+        }
+    ++g.searches;
+    return done(YAMS_OK);
+}
+
+void ds_free_doc_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::free(hits); std::free(counts); }
+
+yams_vector_doc_scan_v1 g_vector_doc_scan = {YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION, nullptr, GUARDED(ds_corpus_set_documents),
+                                             GUARDED(ds_search_docs), GUARDED(ds_free_doc_hits)};
 
 // ---- content_hash_v1 --------------------------------------------------------------------------
 // Every call leases one of the plugin's work contexts (own stream, own workspace), so hashing, chunking
@@ -1414,6 +1543,10 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
     if (std::strcmp(iface_id, YAMS_IFACE_VECTOR_SCAN_V1) == 0) {
         if (version < 1 || version > YAMS_IFACE_VECTOR_SCAN_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
         *out_iface = &g_vector_scan; return YAMS_PLUGIN_OK;
+    }
+    if (std::strcmp(iface_id, YAMS_IFACE_VECTOR_DOC_SCAN_V1) == 0) { // (not in the manifest: see the header)
+        if (version < 1 || version > YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
+        *out_iface = &g_vector_doc_scan; return YAMS_PLUGIN_OK;
     }
     if (std::strcmp(iface_id, YAMS_IFACE_CONTENT_HASH_V1) == 0) {
         if (version < 1 || version > YAMS_IFACE_CONTENT_HASH_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
