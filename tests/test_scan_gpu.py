@@ -1946,6 +1946,29 @@ def test_clustered_corpus_is_proven_by_the_int8_retry(acc, oracle):
     assert r2.diag["exact_fallback_queries"] == 0, r2.diag
 
 
+def test_sliced_call_sums_the_retried_queries_of_its_slices(oracle):
+    """A call of more than 4096 queries runs as slices (yams_scan_topk_device) and reports the sum of their diagnostics — the
+    int8 retry's count included.  The clustered corpus of the retry test: its first slice retries, on a context of its own;
+    queries from every slice, their rows, order and score bits equal the oracle's."""
+    import torch
+    from yams_amd.accel import Accel
+    nq, k = 4160, 100
+    corpus, q = _clustered(300_000, 256, 230, 71, nq)
+    fresh = Accel(0, torch.cuda.current_stream().cuda_stream)
+    try:
+        r = run(fresh, corpus, q, k, shadow="i8")
+    finally:
+        fresh.close()
+    assert r.diag["retried_queries"] > 0, r.diag
+    assert r.diag["rows_visited"] == nq * corpus.shape[0] and r.diag["filter_tier"] == _lib.TIER_I8, r.diag
+    for qi in (0, 1, 1023, 1024, 2047, 3071, 4095, 4096, nq - 1):
+        rows, sims, _, _ = oracle.scan_cosine(corpus, q[qi], k, -1.0, None)
+        cnt = int(r.counts[qi])
+        assert cnt == len(rows), (qi, cnt, len(rows), r.diag)
+        assert np.array_equal(r.rows[qi, :cnt], rows), (qi, r.rows[qi, :cnt][:10], rows[:10])
+        assert np.array_equal(r.scores[qi, :cnt].view(np.uint32), sims.view(np.uint32)), qi
+
+
 def test_tight_clusters_are_listed_whole_in_the_first_pass(acc, oracle):
     """The proof-aware threshold (tau_select_kernel, round 6): 1430 clusters of ~1050 rows whose similarities to a query of
     their own cluster lie within a fraction of the int8 bound's width.  For the queries whose cluster has 16 or more rows in

@@ -44,13 +44,12 @@ struct yams_accel_ctx {
     // What this context has learnt about a corpus's first filter tier (scan_api.cpp, "tier hint"): the int8 tier's bound is as
     // wide as the shadow's quantisation residue — on strongly anisotropic rows (a few large components, a long tail of small
     // ones) five times wider than on isotropic ones, and every query then fails its proof and pays a split-bf16 sweep on top.
-    // Keyed by the int8 shadow's address; `bf16_first` batches start on the bf16 tier, every 256th one probes int8 again.
+    // Keyed by the corpus rows' address (corpus->rows); `bf16_first` batches start on the bf16 tier, every 256th one probes int8 again.
     // depth: what the int8 tier's batches on this corpus needed — 0: the plan's stage 1 (3k + 64 candidates) proves them;
     // 1: most proofs needed the whole list (stage 1 re-scores all of it at once); 2: and many lists were too short (deeper lists)
     // (depth per tier — [0] the int8 tier, [1] the single-pass bf16 tier: the same corpus may crowd one bound and not the other)
     struct TierHint { uint64_t n_rows = 0; bool bf16_first = false; uint32_t served = 0; uint8_t depth[2] = {0, 0}; uint32_t served_deep[2] = {0, 0}; };
     std::map<const void*, TierHint> tier_hints;
-    uint32_t emu_calls = 0; // measurement build: batches this context has served (emulation knobs of scan_api.cpp)
     // pinned host staging
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -155,6 +154,19 @@ hipError_t big_take(int device, size_t bytes, void** p, size_t* cap);
 void big_give(int device, void* p, size_t cap);
 size_t big_trim(int device); // device < 0: every device; returns the bytes freed
 size_t big_held(int device); // bytes the pool holds for this device (free memory as far as a caller sizing its batches is concerned)
+
+// Adds one search's work counters to another's (the slices of a call, the shards of a sharded search).  `path`,
+// `filter_tier` and `returned_rows` follow each caller's own rule.
+inline void diag_add(yams_scan_diag_t& total, const yams_scan_diag_t& d) {
+    total.rows_visited += d.rows_visited;
+    total.exact_distance_evaluations += d.exact_distance_evaluations;
+    total.filter_candidates += d.filter_candidates;
+    total.rescored_rows += d.rescored_rows;
+    total.widened_queries += d.widened_queries;
+    total.exact_fallback_queries += d.exact_fallback_queries;
+    total.escalated_queries += d.escalated_queries;
+    total.retried_queries += d.retried_queries;
+}
 
 #define YA_HIP(ctx, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) \
     return ::yams_accel::hip_fail((ctx), e__, #expr); } while (0)

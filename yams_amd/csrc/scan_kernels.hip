@@ -975,10 +975,7 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
             // similarity — |score - cos| <= err_bound on the bf16 / f32 tiers, cos <= score on the int8 tier (err_bound 0)
             if (a.stat_rescored && !a.all_rows_listed && !a.rank_row) {
                 const double fs = static_cast<double>(key_score(ck));
-                if (a.err_bound > 0.0 ? fabs(sd - fs) > a.err_bound + 1e-7 : sd > fs + 1e-7) {
-                    const unsigned long long nth = atomicAdd(a.stat_rescored + 4, 1ull);
-                    if (nth < 6 && a.stat_rescored[6] == 0x5eed) printf("  honesty: query %u cand %u row %u exact %.7f filter %.7f bound %.5f nsq %.6g\n", q, c, row, sd, fs, a.err_bound, nsq);
-                }
+                if (a.err_bound > 0.0 ? fabs(sd - fs) > a.err_bound + 1e-7 : sd > fs + 1e-7) atomicAdd(a.stat_rescored + 4, 1ull);
                 atomicAdd(a.stat_rescored + 5, 1ull);
             }
 #endif
@@ -995,10 +992,7 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
             // folded into it); rows the int8 tier lists unconditionally (no usable norm) carry +inf
             if (a.stat_rescored && !a.all_rows_listed && !a.rank_row) {
                 const double g = dot - 0.5 * nsq, fs = static_cast<double>(key_score(ck));
-                if (g > fs + 1e-6 * (fabs(dot) + 0.5 * nsq) + 1e-30) {
-                    const unsigned long long nth = atomicAdd(a.stat_rescored + 4, 1ull);
-                    if (nth < 6 && a.stat_rescored[6] == 0x5eed) printf("  honesty (L2): query %u cand %u row %u g %.9g filter %.9g nsq %.6g\n", q, c, row, g, fs, nsq);
-                }
+                if (g > fs + 1e-6 * (fabs(dot) + 0.5 * nsq) + 1e-30) atomicAdd(a.stat_rescored + 4, 1ull);
                 atomicAdd(a.stat_rescored + 5, 1ull);
             }
 #endif

@@ -882,13 +882,7 @@ yams_status_t wait_impl(yams_scan_sharded* s, uint32_t lane, float* out_scores_h
         if (s->n > 1)
             for (uint32_t i = 0; i < s->n; ++i) {
                 const yams_scan_diag_t& d = L.dg[i];
-                diag->rows_visited += d.rows_visited;
-                diag->exact_distance_evaluations += d.exact_distance_evaluations;
-                diag->filter_candidates += d.filter_candidates;
-                diag->rescored_rows += d.rescored_rows;
-                diag->widened_queries += d.widened_queries;
-                diag->exact_fallback_queries += d.exact_fallback_queries;
-                diag->escalated_queries += d.escalated_queries;
+                diag_add(*diag, d);
                 diag->path = std::max(diag->path, d.path);
                 diag->filter_tier = std::max(diag->filter_tier, d.filter_tier);
             }
