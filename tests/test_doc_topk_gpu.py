@@ -5,58 +5,15 @@ matching-row counts must be identical."""
 import numpy as np
 import pytest
 
-from _doc_select import best_per_document
+from _doc_oracle import NO_DOC, expected, run  # noqa: F401  (run and NO_DOC: also used by test_doc_topk_plugin_gpu.py)
 from yams_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-NO_DOC = _lib.NO_DOC
 
-
-def expected(oracle, rows, q, k, thr, row_doc, tie=None, doc_rank=None, allowed=None):
-    """(rows, scores, docs, matching) of one query: the oracle's matching rows, then the restated reduction.  Chunk ids
-    and document hashes are the zero-padded ranks, so that byte order is rank order."""
-    n = rows.shape[0]
-    sel = np.arange(n) if allowed is None else np.asarray(allowed, np.int64)
-    tie = np.arange(n, dtype=np.uint64) if tie is None else tie.astype(np.uint64)
-    r = oracle.scan_cosine(rows[sel], q, max(len(sel), 1), thr, tie_rank=tie[sel]) if len(sel) else (np.zeros(0, np.int64), np.zeros(0, np.float32), 0, 0)
-    assert r is not None
-    m_rows, m_sc = sel[r[0]], r[1]
-    n_docs = int(row_doc[row_doc != NO_DOC].max()) + 1 if (row_doc != NO_DOC).any() else 0
-    rank = np.arange(max(n_docs, 1)) if doc_rank is None else doc_rank
-    hashes = ["" if row_doc[i] == NO_DOC else "%010d" % rank[row_doc[i]] for i in m_rows]
-    best = best_per_document(m_rows, m_sc, ["%010d" % tie[i] for i in m_rows], hashes, k)
-    out_rows = np.array([b[0] for b in best], np.int64)
-    return out_rows, np.array([b[1] for b in best], np.float32), row_doc[out_rows] if len(out_rows) else np.zeros(0, np.uint32), len(m_rows)
-
-
-def run(acc, rows, queries, k, thr, row_doc, n_docs, tie=None, doc_rank=None, mask_rows=None, row_base=0, flags=0, metric=0):
-    n, d = rows.shape
-    bufs = [acc.to_device(rows), acc.to_device(row_doc.astype(np.uint32))]
-    tie_p = inv_p = rank_p = mask_p = None
-    if tie is not None:
-        inv = np.empty_like(tie); inv[tie] = np.arange(n, dtype=tie.dtype)
-        bufs += [acc.to_device(tie.astype(np.uint32)), acc.to_device(inv.astype(np.uint32))]
-        tie_p, inv_p = bufs[-2].ptr, bufs[-1].ptr
-    if doc_rank is not None:
-        bufs.append(acc.to_device(doc_rank.astype(np.uint32))); rank_p = bufs[-1].ptr
-    count = 0
-    if mask_rows is not None:
-        words = np.zeros((n + 31) // 32, np.uint32)
-        for r in mask_rows:
-            words[r >> 5] |= np.uint32(1 << (r & 31))
-        bufs.append(acc.to_device(words)); mask_p = bufs[-1].ptr; count = len(set(int(r) for r in mask_rows))
-    try:
-        v = acc.corpus_view(bufs[0].ptr, n, d, tie_rank_ptr=tie_p, rank_row_ptr=inv_p, row_base=row_base, row_mask_ptr=mask_p,
-                            row_mask_count=count)
-        return acc.scan_doc_topk(v, acc.docs_view(bufs[1].ptr, n_docs, rank_p), queries, k, thr, metric=metric, flags=flags)
-    finally:
-        for b in bufs:
-            b.free()
-
-
-def check(acc, oracle, rows, queries, k, thr, row_doc, n_docs, tie=None, doc_rank=None, mask_rows=None, row_base=0, qsample=None):
-    res = run(acc, rows, queries, k, thr, row_doc, n_docs, tie, doc_rank, mask_rows, row_base)
+def check(acc, oracle, rows, queries, k, thr, row_doc, n_docs, tie=None, doc_rank=None, mask_rows=None, row_base=0, qsample=None,
+          rows_offset=0):
+    res = run(acc, rows, queries, k, thr, row_doc, n_docs, tie, doc_rank, mask_rows, row_base, rows_offset=rows_offset)
     allowed = None if mask_rows is None else np.unique(np.asarray(mask_rows, np.int64))
     n_eff = rows.shape[0] if allowed is None else len(allowed)
     assert res.diag["used_exact_scan"] == 1 and res.diag["path"] == 1
@@ -199,3 +156,118 @@ def test_query_slices_of_the_document_workspace(acc, oracle):
     queries = rng.standard_normal((600, d)).astype(np.float32)
     check(acc, oracle, rows, queries, 25, 0.3, row_doc, n_docs, tie=rng.permutation(n).astype(np.uint32),
           qsample=[0, 15, 16, 17, 300, 599])
+
+
+@pytest.mark.parametrize("d,offset", [(1, 0), (3, 0), (33, 0), (385, 0), (128, 1), (33, 1)])
+def test_scalar_staging_of_rows_that_are_not_16_byte_loads(acc, oracle, d, offset):
+    """doc_score_kernel stages a row with 16-byte loads only when dim % 4 == 0 and the row pointer is 16-byte aligned;
+    every other shape goes through the scalar staging and its tail bound (the last 1-3 elements of a 32-element chunk)."""
+    rng = np.random.default_rng(400 + d + offset)
+    n, n_docs = 2_500, 300
+    rows = corpus(rng, n, d, special=d >= 6)
+    row_doc = layout(rng, n, n_docs, "random")
+    row_doc[rng.choice(n, 50, replace=False)] = NO_DOC
+    queries = rng.standard_normal((5, d)).astype(np.float32)
+    queries[1] = rows[3] * np.float32(1.5)
+    check(acc, oracle, rows, queries, 40, -1.0, row_doc, n_docs, tie=rng.permutation(n).astype(np.uint32),
+          doc_rank=rng.permutation(n_docs).astype(np.uint32), rows_offset=offset)
+    check(acc, oracle, rows, queries[:1], 7, 0.05, row_doc, n_docs, rows_offset=offset)
+
+
+@pytest.mark.parametrize("nq", [2, 4, 5, 9])
+def test_query_group_forms(acc, oracle, nq):
+    """QG = 4 for 2-4 queries, 8 above (a ragged last group for 5 and 9): every query of the group against the oracle."""
+    rng = np.random.default_rng(500 + nq)
+    n, d, n_docs = 5_000, 64, 700
+    rows = corpus(rng, n, d)
+    row_doc = layout(rng, n, n_docs, "contiguous")
+    queries = rng.standard_normal((nq, d)).astype(np.float32)
+    queries[nq - 1] = rows[10] * np.float32(0.5)
+    check(acc, oracle, rows, queries, 30, -1.0, row_doc, n_docs, tie=rng.permutation(n).astype(np.uint32))
+
+
+@pytest.mark.parametrize("nq", [17, 19])
+def test_last_query_slice_of_one_and_of_three_queries(acc, oracle, nq):
+    """1 M document ordinals: a slice holds 256 MiB / (16 * 1 M) = 16 queries, so 17 and 19 queries leave a last slice of
+    1 (QG = 1) and of 3 (QG = 4) queries at q0 = 16: their query vectors, norms and matching counters are offset."""
+    n, d, n_docs = 20_000, 36, 1_000_000
+    rng = np.random.default_rng(600 + nq)
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    row_doc = rng.choice(n_docs, n, replace=False).astype(np.uint32)
+    row_doc[:3000] = row_doc[0]
+    queries = rng.standard_normal((nq, d)).astype(np.float32)
+    queries[16] = rows[5] * np.float32(3.0)
+    check(acc, oracle, rows, queries, 20, 0.1, row_doc, n_docs, doc_rank=rng.permutation(n_docs).astype(np.uint32),
+          qsample=[0, 15] + list(range(16, nq)))
+
+
+def test_document_runs_at_wave_and_workgroup_edges(acc, oracle):
+    """The segmented max over runs of equal documents inside a wave: runs that start and end on, one before and one after
+    64- and 256-row edges, single-row runs, and runs spanning several workgroups; a dense and a sparse (gathered) mask."""
+    rng = np.random.default_rng(77)
+    runs = [64, 64, 1, 63, 65, 127, 1, 256, 255, 257, 2, 512, 190, 66, 700, 1, 1, 64]
+    n, d = sum(runs), 48
+    rows = corpus(rng, n, d)
+    row_doc = np.repeat(np.arange(len(runs)) * 3 % len(runs), runs).astype(np.uint32)
+    queries = rng.standard_normal((9, d)).astype(np.float32)
+    check(acc, oracle, rows, queries, 18, -1.0, row_doc, len(runs), tie=rng.permutation(n).astype(np.uint32))
+    check(acc, oracle, rows, queries, 18, -1.0, row_doc, len(runs), mask_rows=np.nonzero(rng.random(n) < 0.6)[0])
+    check(acc, oracle, rows, queries, 18, -1.0, row_doc, len(runs), mask_rows=np.nonzero(rng.random(n) < 0.05)[0])
+
+
+def test_mask_at_the_sparse_dense_switch(acc, oracle):
+    """A mask of fewer than n_rows / 8 rows is gathered first, one of n_rows / 8 or more is read in place: 511, 512 and
+    513 allowed rows of 4096."""
+    rng = np.random.default_rng(88)
+    n, d, n_docs = 4096, 40, 333
+    rows = corpus(rng, n, d)
+    row_doc = layout(rng, n, n_docs, "random")
+    queries = rng.standard_normal((3, d)).astype(np.float32)
+    for cnt in (511, 512, 513):
+        mask = np.sort(rng.choice(n, cnt, replace=False))
+        check(acc, oracle, rows, queries, 25, -1.0, row_doc, n_docs, mask_rows=mask, row_base=5)
+
+
+def test_refusals_leave_the_context_usable(acc, oracle):
+    """A doc_rank that is not a permutation (a repeated rank, every rank in range), a striped shard and a tie_rank without
+    rank_row are refused; the next call on the same context is served."""
+    rng = np.random.default_rng(99)
+    n, d, n_docs = 3000, 64, 120
+    rows = corpus(rng, n, d)
+    row_doc = layout(rng, n, n_docs, "random")
+    queries = rng.standard_normal((3, d)).astype(np.float32)
+    rep = rng.permutation(n_docs).astype(np.uint32)
+    rep[17] = rep[90]                                      # rank rep[90] twice, one rank missing
+    with pytest.raises(_lib.AccelError) as e:
+        run(acc, rows, queries, 10, -1.0, row_doc, n_docs, doc_rank=rep)
+    assert e.value.status == _lib.YAMS_ERR_INVALID_ARG
+    check(acc, oracle, rows, queries, 10, -1.0, row_doc, n_docs, doc_rank=rng.permutation(n_docs).astype(np.uint32))
+    d_rows, d_doc, d_tie = acc.to_device(rows), acc.to_device(row_doc), acc.to_device(np.arange(n, dtype=np.uint32))
+    try:
+        dv = acc.docs_view(d_doc.ptr, n_docs)
+        with pytest.raises(_lib.AccelError) as e:
+            acc.scan_doc_topk(acc.corpus_view(d_rows.ptr, n, d, stripe_rows=1024, n_stripes=3), dv, queries, 10, -1.0)
+        assert e.value.status == _lib.YAMS_ERR_UNSUPPORTED
+        check(acc, oracle, rows, queries, 10, -1.0, row_doc, n_docs)
+        with pytest.raises(_lib.AccelError) as e:
+            acc.scan_doc_topk(acc.corpus_view(d_rows.ptr, n, d, tie_rank_ptr=d_tie.ptr), dv, queries, 10, -1.0)
+        assert e.value.status == _lib.YAMS_ERR_INVALID_ARG
+        check(acc, oracle, rows, queries, 10, -1.0, row_doc, n_docs)
+    finally:
+        for b in (d_rows, d_doc, d_tie):
+            b.free()
+
+
+def test_randomised_doc_stress_against_the_oracle():
+    """tests/stress_doc.py: random dims (scalar and 16-byte staging), query groups and slices, document counts around the
+    select cap, layouts with runs at wave / workgroup edges, masks at the sparse / dense switch, tie and document ranks;
+    every checked query bit-exact against the oracle + the restated reduction, and every path reached."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "stress_doc.py"), "--cases", "240", "--seed", "5"],
+                       capture_output=True, text=True, timeout=280)
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and line, r.stdout[-2000:] + r.stderr[-2000:]
+    res = json.loads(line[-1])
+    assert res["cases"] == 240 and res["mismatches"] == 0 and res["checked_queries"] >= 240, res
+    assert all(v > 0 for v in res["paths"].values()), res["paths"]

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import _pq
+from yams_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -197,3 +198,190 @@ def test_filtered_adc_scan_falls_back_where_its_lists_are_no_use(acc, oracle):
             assert cnt == len(rows) and r.rows[qi, :cnt].tolist() == rows.tolist(), (qi, cand is None, r.diag)
             assert np.array_equal(r.scores[qi, :cnt].view(np.uint32), sims.view(np.uint32)), qi
     d_rows.free()
+
+
+def _call(acc, corpus, codes, luts, queries, k, rf=2, lanes=1, keys=None, roi=None, cand=None):
+    d_rows = acc.to_device(corpus)
+    try:
+        v = acc.corpus_view(d_rows.ptr, corpus.shape[0], corpus.shape[1])
+        return acc.scan_pq_topk(v, codes, luts, queries, k, -1.0, rf, tie_keys=keys, row_of_index=roi, candidates=cand, sum_lanes=lanes)
+    finally:
+        d_rows.free()
+
+
+def _same(oracle, r, corpus, codes, luts, queries, k, qs, rf=2, lanes=1, keys=None, roi=None, cand=None):
+    for qi in qs:
+        rows, sims, _ = oracle.pq_search(corpus, codes, luts[qi], queries[qi], k, -1.0, rf, tie_keys=keys, row_of_index=roi,
+                                         candidates=cand, sum_lanes=lanes)
+        cnt = int(r.counts[qi])
+        assert cnt == len(rows) and r.rows[qi, :cnt].tolist() == rows.tolist(), (qi, cnt, len(rows), r.diag)
+        assert np.array_equal(r.scores[qi, :cnt].view(np.uint32), sims.view(np.uint32)), qi
+
+
+@pytest.mark.parametrize("m", [7, 32, 33, 37, 64, 65, 100, 127, 128])
+def test_unfiltered_adc_keys_at_every_group_size_and_code_load(acc, oracle, m):
+    """pq_adc_keys_kernel (indexes under 65 536 entries): four query tables per workgroup for m <= 32, two for m <= 64, one
+    above, fewer when the batch holds fewer queries (1, 2, 3, 9 queries); code bytes read as words when m % 4 == 0 and one
+    at a time otherwise; under every served sum order.  Random tables: every query has its own."""
+    n, d = 6_000, 48
+    rng = np.random.default_rng(700 + m)
+    corpus = oracle.synth_rows(700 + m, 0, 3_000, d)
+    codes, keys, roi = _random_index(rng, n, m, d, n_rows=3_000)
+    codes[100:130] = codes[99]                                               # equal ADC scores: the tie key decides
+    queries = oracle.synth_rows(700 + m, 1 << 40, 9, d)
+    luts = rng.standard_normal((9, m, 256)).astype(np.float32)
+    for lanes in (1, 4, 8, 16):
+        for nq in (1, 2, 3, 9):
+            r = _call(acc, corpus, codes, luts[:nq], queries[:nq], 15, 3, lanes, keys, roi)
+            assert r.diag["exact_fallback_queries"] == nq, r.diag             # all through the unfiltered form
+            _same(oracle, r, corpus, codes, luts, queries, 15, range(nq), 3, lanes, keys, roi)
+
+
+def test_unfiltered_form_in_more_than_one_key_batch(acc, oracle):
+    """Unfiltered keys run in batches of 2^31 / (8 * n_items) queries: 4 500 queries over 60 000 codes are a batch of 4 473
+    and one of 27.  Every query has its own table, so a batch that reads or writes another batch's slots is visible on
+    both sides of the boundary."""
+    n, m, d, nq = 60_000, 4, 16, 4_500
+    rng = np.random.default_rng(801)
+    corpus = oracle.synth_rows(801, 0, 5_000, d)
+    codes, keys, roi = _random_index(rng, n, m, d, n_rows=5_000)
+    queries = oracle.synth_rows(801, 1 << 40, nq, d)
+    luts = rng.standard_normal((nq, m, 256)).astype(np.float32)
+    batch = (1 << 31) // (8 * n)
+    assert batch == 4473
+    r = _call(acc, corpus, codes, luts, queries, 10, 2, 1, keys, roi)
+    assert r.diag["exact_fallback_queries"] == nq, r.diag
+    _same(oracle, r, corpus, codes, luts, queries, 10, [0, 1, 2000, batch - 1, batch, batch + 1, nq - 2, nq - 1], 2, 1, keys, roi)
+
+
+@pytest.mark.parametrize("lanes,k,rf", [(1, 100, 4), (8, 300, 2), (16, 1000, 2)])
+def test_filtered_form_with_a_threshold_rank_above_256(acc, oracle, lanes, k, rf):
+    """65 536 entries: a sample stride of 4, and approxK >= 300 asks tau_select_kernel for a rank above 256 (its radix
+    branch).  Well-spread tables: a wrong threshold would only send queries to the unfiltered form, so none may go there."""
+    n, m, d = 65_536, 16, 128
+    rng = np.random.default_rng(900 + k)
+    corpus = oracle.synth_rows(900, 0, 8_000, d)
+    pq = _pq.Pq(_pq.unit(corpus), m, 900)
+    codes, keys, roi = _random_index(rng, n, m, d)
+    queries = oracle.synth_rows(900 + k, 1 << 40, 9, d)
+    luts = np.stack([pq.lut(q) for q in queries])
+    r = _call(acc, corpus, codes, luts, queries, k, rf, lanes, keys, roi)
+    assert r.diag["exact_fallback_queries"] == 0, r.diag
+    _same(oracle, r, corpus, codes, luts, queries, k, range(9), rf, lanes, keys, roi)
+
+
+@pytest.mark.parametrize("m", [36, 37, 72, 73])
+def test_filtered_form_on_both_sides_of_its_group_boundaries(acc, oracle, m):
+    """pq_adc_filter_kernel holds four query tables per workgroup up to m = 36, two up to 72, one above."""
+    n, d = 70_000, m * 4
+    rng = np.random.default_rng(1000 + m)
+    corpus = oracle.synth_rows(1000 + m, 0, 6_000, d)
+    pq = _pq.Pq(_pq.unit(corpus), m, 1000 + m)
+    codes, keys, roi = _random_index(rng, n, m, d, n_rows=6_000)
+    queries = oracle.synth_rows(1000 + m, 1 << 40, 7, d)
+    luts = np.stack([pq.lut(q) for q in queries])
+    r = _call(acc, corpus, codes, luts, queries, 20, 2, 4, keys, roi)
+    assert r.diag["exact_fallback_queries"] == 0, r.diag
+    _same(oracle, r, corpus, codes, luts, queries, 20, range(7), 2, 4, keys, roi)
+
+
+def test_index_sizes_and_candidate_lists_at_the_filtered_switch(acc, oracle):
+    """65 535 entries take the unfiltered form, 65 536 and 65 537 the filtered one; the same for candidate lists of 65 535 and
+    exactly 65 536 indices out of a larger index."""
+    m, d = 8, 64
+    rng = np.random.default_rng(1100)
+    corpus = oracle.synth_rows(1100, 0, 4_000, d)
+    pq = _pq.Pq(_pq.unit(corpus), m, 1100)
+    codes, keys, roi = _random_index(rng, 90_000, m, d, n_rows=4_000)
+    queries = oracle.synth_rows(1100, 1 << 40, 5, d)
+    luts = np.stack([pq.lut(q) for q in queries])
+    for n in (65_535, 65_536, 65_537):
+        r = _call(acc, corpus, codes[:n], luts, queries, 12, 2, 1, keys[:n], roi[:n])
+        assert r.diag["exact_fallback_queries"] == (5 if n < 65_536 else 0), (n, r.diag)
+        _same(oracle, r, corpus, codes[:n], luts, queries, 12, range(5), 2, 1, keys[:n], roi[:n])
+    for c in (65_535, 65_536):
+        cand = np.sort(rng.choice(90_000, c, replace=False)).astype(np.uint32)
+        r = _call(acc, corpus, codes, luts, queries, 12, 2, 8, keys, roi, cand)
+        assert r.diag["exact_fallback_queries"] == (5 if c < 65_536 else 0), (c, r.diag)
+        _same(oracle, r, corpus, codes, luts, queries, 12, range(5), 2, 8, keys, roi, cand)
+
+
+def test_limits_of_approx_k_and_m(acc, oracle):
+    """approxK = min(candidates, max(k, k * rerank_factor)): 2047 is served, 2048 refused, and a k * rerank_factor above 2047
+    is served when the index caps approxK; m = 128 is served, 129 refused.  A refusal leaves the context usable."""
+    d = 32
+    rng = np.random.default_rng(1200)
+    corpus = oracle.synth_rows(1200, 0, 3_000, d)
+    queries = oracle.synth_rows(1200, 1 << 40, 2, d)
+    codes, keys, roi = _random_index(rng, 5_000, 8, d, n_rows=3_000)
+    luts = rng.standard_normal((2, 8, 256)).astype(np.float32)
+    r = _call(acc, corpus, codes, luts, queries, 89, 23, 1, keys, roi)              # 89 * 23 = 2047
+    assert r.diag["filter_candidates"] == 2 * 2047, r.diag
+    _same(oracle, r, corpus, codes, luts, queries, 89, range(2), 23, 1, keys, roi)
+    for k, rf in ((1024, 2), (683, 3)):                                              # 2048, 2049
+        with pytest.raises(_lib.AccelError) as e:
+            _call(acc, corpus, codes, luts, queries, k, rf, 1, keys, roi)
+        assert e.value.status == _lib.YAMS_ERR_UNSUPPORTED, (k, rf)
+    for n in (2_047, 1_500):                                                         # capped by the index
+        r = _call(acc, corpus, codes[:n], luts, queries, 1024, 16, 1, keys[:n], roi[:n])
+        assert r.diag["filter_candidates"] == 2 * n, r.diag
+        _same(oracle, r, corpus, codes[:n], luts, queries, 1024, range(2), 16, 1, keys[:n], roi[:n])
+    cand = np.sort(rng.choice(5_000, 2_000, replace=False)).astype(np.uint32)      # ... or by the candidate list
+    r = _call(acc, corpus, codes, luts, queries, 1000, 4, 1, keys, roi, cand)
+    _same(oracle, r, corpus, codes, luts, queries, 1000, range(2), 4, 1, keys, roi, cand)
+    codes128, keys128, roi128 = _random_index(rng, 3_000, 128, d, n_rows=3_000)
+    luts128 = rng.standard_normal((2, 128, 256)).astype(np.float32)
+    r = _call(acc, corpus, codes128, luts128, queries, 10, 2, 16, keys128, roi128)
+    _same(oracle, r, corpus, codes128, luts128, queries, 10, range(2), 2, 16, keys128, roi128)
+    codes129 = rng.integers(0, 256, (3_000, 129)).astype(np.uint8)
+    with pytest.raises(_lib.AccelError) as e:
+        _call(acc, corpus, codes129, rng.standard_normal((2, 129, 256)).astype(np.float32), queries, 10)
+    assert e.value.status == _lib.YAMS_ERR_UNSUPPORTED
+    r = _call(acc, corpus, codes, luts, queries, 10, 2, 1, keys, roi)
+    _same(oracle, r, corpus, codes, luts, queries, 10, range(2), 2, 1, keys, roi)
+
+
+def test_misaligned_codes_or_tables_are_refused(acc, oracle):
+    """Codes must be 4-byte and tables 16-byte aligned (the kernels read words and 16-byte vectors): a pointer 1 byte (codes)
+    or 4 bytes (tables) past an aligned one is refused before anything runs; the context stays usable."""
+    import ctypes as C
+    n, m, d = 2_000, 8, 32
+    rng = np.random.default_rng(1300)
+    corpus = oracle.synth_rows(1300, 0, n, d)
+    codes = rng.integers(0, 256, (n, m)).astype(np.uint8)
+    queries = oracle.synth_rows(1300, 1 << 40, 2, d)
+    luts = rng.standard_normal((2, m, 256)).astype(np.float32)
+    d_rows = acc.to_device(corpus)
+    d_codes = acc.to_device(np.concatenate([np.zeros(16, np.uint8), codes.ravel()]))
+    d_luts = acc.to_device(np.concatenate([np.zeros(4, np.float32), luts.ravel()]))
+    d_q = acc.to_device(queries)
+    outs = [acc.alloc(2 * 10 * 4), acc.alloc(2 * 10 * 8), acc.alloc(2 * 4)]
+    try:
+        v = acc.corpus_view(d_rows.ptr, n, d)
+        prm = _lib.ScanPqParams(10, -1.0, 2, 0)
+        for c_off, l_off in ((1, 16), (2, 16), (16, 4), (16, 8)):
+            pq = _lib.ScanPqIndex(d_codes.ptr + c_off, n, m, 0, None, None)
+            diag = _lib.ScanDiag()
+            st = acc.L.yams_scan_pq_topk_device(acc.ctx, C.byref(v), C.byref(pq), d_q.ptr, d_luts.ptr + l_off, 2, C.byref(prm), None, 0,
+                                                outs[0].ptr, outs[1].ptr, outs[2].ptr, C.byref(diag))
+            assert st == _lib.YAMS_ERR_INVALID_ARG, (c_off, l_off, st)
+    finally:
+        for b in [d_rows, d_codes, d_luts, d_q] + outs:
+            b.free()
+    r = _call(acc, corpus, codes, luts, queries, 10)
+    _same(oracle, r, corpus, codes, luts, queries, 10, range(2))
+
+
+def test_randomised_pq_stress_against_the_oracle():
+    """tests/stress_pq.py: random index sizes around the filtered switch, m across every group boundary of both ADC kernels,
+    every sum order, k / rerank factors up to approxK 2047, row maps with lost rows, candidate lists, refused queries,
+    fallback-forcing tables and multi-batch query sets; every checked query bit-exact against the oracle, every path reached."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "stress_pq.py"), "--cases", "160", "--seed", "3"],
+                       capture_output=True, text=True, timeout=280)
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and line, r.stdout[-2000:] + r.stderr[-2000:]
+    res = json.loads(line[-1])
+    assert res["cases"] == 160 and res["calls"] == 160 and res["mismatches"] == 0 and res["checked_queries"] >= 160, res
+    assert all(v > 0 for v in res["paths"].values()), res["paths"]
