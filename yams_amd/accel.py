@@ -79,9 +79,11 @@ class DedupSet:
         acc._check(acc.L.yams_dedup_set_create(acc.ctx, expected_entries, C.byref(self.h)))
 
     def close(self):
-        if self.h:
+        # yams_dedup_set_destroy uses the set's context: once the Accel is closed there is nothing left to call it
+        # on (a set kept alive past the context, e.g. by a traceback, is dropped with the process)
+        if self.h and getattr(self.acc, "ctx", None):
             self.acc.L.yams_dedup_set_destroy(self.h)
-            self.h = None
+        self.h = None
 
     def __del__(self):
         try:

@@ -20,7 +20,7 @@ void free_table(DedupTable& t) {
     if (t.tags) (void)hipFree(t.tags);
     if (t.keys) (void)hipFree(t.keys);
     if (t.owner) (void)hipFree(t.owner);
-    if (t.fresh) (void)hipFree(t.fresh);
+    if (t.state) (void)hipFree(t.state);
     t = DedupTable{};
 }
 
@@ -29,13 +29,13 @@ yams_status_t alloc_table(yams_accel_ctx* ctx, uint32_t capacity, DedupTable* ou
     t.capacity = capacity;
     const size_t c = capacity;
     if (ya_malloc(reinterpret_cast<void**>(&t.tags), c * 8) != hipSuccess || ya_malloc(reinterpret_cast<void**>(&t.keys), c * 32) != hipSuccess ||
-        ya_malloc(reinterpret_cast<void**>(&t.owner), c * 4) != hipSuccess || ya_malloc(reinterpret_cast<void**>(&t.fresh), c) != hipSuccess) {
+        ya_malloc(reinterpret_cast<void**>(&t.owner), c * 4) != hipSuccess || ya_malloc(reinterpret_cast<void**>(&t.state), c) != hipSuccess) {
         (void)hipGetLastError();
         free_table(t);
         return fail(ctx, YAMS_ERR_RESOURCE_EXHAUSTED, "out of device memory for the digest set");
     }
     YA_HIP(ctx, hipMemsetAsync(t.tags, 0, c * 8, ctx->stream));
-    YA_HIP(ctx, hipMemsetAsync(t.fresh, 0, c, ctx->stream));
+    YA_HIP(ctx, hipMemsetAsync(t.state, 0, c, ctx->stream));
     YA_HIP(ctx, launch_dedup_fill_owner(ctx->stream, t.owner, capacity));
     *out = t;
     return YAMS_OK;
@@ -122,14 +122,21 @@ yams_status_t yams_dedup_insert_device(yams_dedup_set* s, const uint8_t* digests
     YA_TRY(pinned_get(ctx, 64, (void**)&h_unres));
     const uint64_t* d64 = reinterpret_cast<const uint64_t*>(digests);
     TimedRegion tr(ctx, "dedup_insert");
-    for (int round = 0;; ++round) {
+    // A digest is pending after a round only if it stopped on a slot another key of its tag claimed in that
+    // round; it resumes one slot further.  So in round r (from 0) a pending digest stops at offset >= r of its
+    // probe sequence, and every slot up to there is occupied.  ensure_room keeps at most capacity / 2 slots
+    // occupied, so no digest is pending after capacity / 2 rounds and the guard below cannot trigger.  (Long
+    // same-tag chains cost one round per digest; SHA-256 output does not form them.)
+    const uint64_t max_rounds = s->t.capacity / 2 + 1;
+    bool converged = false;
+    for (uint64_t round = 0; round < max_rounds && !converged; ++round) {
         YA_HIP(ctx, hipMemsetAsync(d_unres, 0, 4, st));
         YA_HIP(ctx, launch_dedup_round(st, s->t, d64, nn, d_pending, d_start, d_slot, out_is_new, d_unres, round == 0));
         YA_HIP(ctx, hipMemcpyAsync(h_unres, d_unres, 4, hipMemcpyDeviceToHost, st));
         YA_HIP(ctx, hipStreamSynchronize(st));
-        if (*h_unres == 0) break;
-        if (round > 64) return fail(ctx, YAMS_ERR_INTERNAL, "digest set did not converge");
+        converged = *h_unres == 0;
     }
+    // (also without convergence: every slot claimed so far holds its owner's key and is settled here)
     YA_HIP(ctx, launch_dedup_settle(st, s->t, nn, d_slot, out_is_new, s->d_count));
     tr.end();
     unsigned long long h[3] = {0, 0, 0};
@@ -144,6 +151,7 @@ yams_status_t yams_dedup_insert_device(yams_dedup_set* s, const uint8_t* digests
     s->count = h[0];
     if (out_bytes_new) *out_bytes_new = h[1];
     if (out_bytes_deduped) *out_bytes_deduped = h[2];
+    if (!converged) return fail(ctx, YAMS_ERR_INTERNAL, "digest set did not converge");
     return YAMS_OK;
 }
 

@@ -6,11 +6,18 @@
 // by the exists() of any later chunk with the same hash.  So chunk i is NEW iff its digest is
 // neither in the store nor carried by an earlier chunk of the same walk.  Here: an open-addressing
 // table keyed by the full 32-byte digest; a batch insert answers is_new[i] with exactly that rule
-// (first occurrence = lowest index, made deterministic with atomicMin), in three race-free steps:
-//   claim   every digest finds the slot that carries its 64-bit tag or claims an empty one (CAS)
-//   write   the lowest-index claimer of a fresh slot writes the full key
-//   verify  every digest compares its 32 bytes with the slot's key; a tag collision with a
-//           different key (2^-64 per pair) resumes probing one slot further in another round.
+// (first occurrence = lowest index, made deterministic with atomicMin), in rounds of three race-free steps:
+//   claim   every pending digest walks from its home (or where it stopped last round).  A slot whose
+//           key is already written (state != kSlotUnwritten: an earlier round or call) is compared in
+//           full: a match answers the digest (not new), a mismatch is passed; an empty slot is claimed
+//           (CAS on the tag); a slot claimed in this round carries no key yet, so a digest stops there
+//           on its 64-bit tag (atomicMin owner)
+//   write   the lowest-index claimer of a slot claimed in this round writes the full key
+//   verify  every digest that stopped on such a slot compares its 32 bytes with the key; a tag
+//           collision with a different key (2^-64 per pair for SHA-256) resumes one slot further in
+//           the next round.
+// A written key is never rewritten.  Digests with equal keys take the same decisions at every slot,
+// so they stop at the same slot in the same round and the owner is their lowest index.
 // Byte/integer work, HBM-latency bound (one random 64-byte slot per digest); no MFMA.
 #include "common.h"
 #include "dedup_launch.h"
@@ -22,71 +29,92 @@ __device__ __forceinline__ uint64_t digest_tag(const uint64_t* d) {
     return t == 0 ? 1ull : t; // 0 marks an empty slot
 }
 
+__device__ __forceinline__ bool same_key(const uint64_t* k, const uint64_t* d) {
+    return k[0] == d[0] && k[1] == d[1] && k[2] == d[2] && k[3] == d[3];
+}
+
+// Home slot of a digest; claim, probe and rehash all start here.  tests/_dedup.py builds digests with
+// chosen homes from this very formula (digest(), home_of()): change the two together, or the tests'
+// collision chains silently stop colliding.
+__device__ __forceinline__ uint32_t dedup_home(const uint64_t* d, uint32_t mask) {
+    return static_cast<uint32_t>((d[1] ^ (d[0] >> 17)) & mask);
+}
+
+// pending[i] between the steps of a round
+constexpr uint8_t kDone = 0;  // answered (is_new[i] is final)
+constexpr uint8_t kRetry = 1; // tag collision with another key: probe on from probe_start[i] next round
+constexpr uint8_t kCheck = 2; // stopped on a slot claimed in this round: write / verify decide
+
 __global__ __launch_bounds__(256) void dedup_claim_kernel(DedupTable t, const uint64_t* digests, uint32_t n,
-                                                          const uint8_t* pending, uint32_t* probe_start,
-                                                          uint32_t* slot_of, int first_round) {
+                                                          uint8_t* pending, uint32_t* probe_start,
+                                                          uint32_t* slot_of, uint8_t* is_new, int first_round) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || (!first_round && !pending[i])) return;
+    if (i >= n || (!first_round && pending[i] != kRetry)) return;
     const uint64_t* d = digests + 4ull * i;
     const uint64_t tag = digest_tag(d);
     const uint32_t mask = t.capacity - 1u;
-    uint32_t s = first_round ? static_cast<uint32_t>((d[1] ^ (d[0] >> 17)) & mask) : probe_start[i];
+    uint32_t s = first_round ? dedup_home(d, mask) : probe_start[i];
     for (;;) {
         unsigned long long* tp = reinterpret_cast<unsigned long long*>(&t.tags[s]);
         unsigned long long cur = *reinterpret_cast<volatile unsigned long long*>(tp);
         if (cur == 0ull) {
             cur = atomicCAS(tp, 0ull, static_cast<unsigned long long>(tag));
-            if (cur == 0ull) { t.fresh[s] = 1; cur = tag; }
+            if (cur == 0ull) { atomicMin(&t.owner[s], i); slot_of[i] = s; pending[i] = kCheck; return; }
         }
         if (cur == tag) {
-            atomicMin(&t.owner[s], i);
-            slot_of[i] = s;
-            return;
+            // state and keys are written only by the write / settle / rehash kernels, so both are stable
+            // here (loaded together): kSlotUnwritten under a non-zero tag means "claimed in this round".
+            const uint8_t st = t.state[s];
+            const bool known = same_key(t.keys + 4ull * s, d);
+            if (st == kSlotUnwritten) { atomicMin(&t.owner[s], i); slot_of[i] = s; pending[i] = kCheck; return; }
+            if (known) { slot_of[i] = s; is_new[i] = 0; pending[i] = kDone; return; } // written by an earlier round or call
         }
         s = (s + 1u) & mask;
     }
 }
 
 __global__ __launch_bounds__(256) void dedup_write_kernel(DedupTable t, const uint64_t* digests, uint32_t n,
-                                                          const uint8_t* pending, const uint32_t* slot_of,
-                                                          int first_round) {
+                                                          const uint8_t* pending, const uint32_t* slot_of) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || (!first_round && !pending[i])) return;
+    if (i >= n || pending[i] != kCheck) return;
     const uint32_t s = slot_of[i];
-    if (t.fresh[s] == 1 && t.owner[s] == i) {
+    if (t.owner[s] == i && t.state[s] == kSlotUnwritten) { // only a slot claimed in this round
         const uint64_t* d = digests + 4ull * i;
         uint64_t* k = t.keys + 4ull * s;
         k[0] = d[0]; k[1] = d[1]; k[2] = d[2]; k[3] = d[3];
+        t.state[s] = kSlotNew;
     }
 }
 
 __global__ __launch_bounds__(256) void dedup_verify_kernel(DedupTable t, const uint64_t* digests, uint32_t n,
                                                            uint8_t* pending, uint32_t* probe_start,
                                                            const uint32_t* slot_of, uint8_t* is_new,
-                                                           unsigned int* n_unresolved, int first_round) {
+                                                           unsigned int* n_unresolved) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || (!first_round && !pending[i])) return;
+    if (i >= n || pending[i] != kCheck) return;
     const uint32_t s = slot_of[i];
     const uint64_t* d = digests + 4ull * i;
-    const uint64_t* k = t.keys + 4ull * s;
-    if (k[0] == d[0] && k[1] == d[1] && k[2] == d[2] && k[3] == d[3]) {
-        is_new[i] = (t.fresh[s] == 1 && t.owner[s] == i) ? 1 : 0;
-        pending[i] = 0;
+    if (same_key(t.keys + 4ull * s, d)) {
+        is_new[i] = (t.state[s] == kSlotNew && t.owner[s] == i) ? 1 : 0;
+        pending[i] = kDone;
     } else { // same tag, different digest: keep probing behind this slot
-        pending[i] = 1;
+        is_new[i] = 0;  // (stays 0 should the call give up: settle then skips it)
+        pending[i] = kRetry;
         probe_start[i] = (s + 1u) & (t.capacity - 1u);
         atomicAdd(n_unresolved, 1u);
     }
 }
 
-// After the last round: slots claimed by this batch become ordinary entries.
+// After the last round: slots claimed by this batch become ordinary entries.  Every such slot has an
+// owner whose key it holds, and that owner is the one digest that reports it new.
 __global__ __launch_bounds__(256) void dedup_settle_kernel(DedupTable t, uint32_t n, const uint32_t* slot_of,
                                                            const uint8_t* is_new, unsigned long long* count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || !is_new[i]) return;
     const uint32_t s = slot_of[i];
-    if (is_new[i]) { t.fresh[s] = 0; atomicAdd(count, 1ull); }
-    t.owner[s] = 0xffffffffu; // benign same-value races
+    t.state[s] = kSlotSettled;
+    t.owner[s] = 0xffffffffu;
+    atomicAdd(count, 1ull);
 }
 
 __global__ __launch_bounds__(256) void dedup_probe_kernel(DedupTable t, const uint64_t* digests, uint32_t n,
@@ -96,14 +124,11 @@ __global__ __launch_bounds__(256) void dedup_probe_kernel(DedupTable t, const ui
     const uint64_t* d = digests + 4ull * i;
     const uint64_t tag = digest_tag(d);
     const uint32_t mask = t.capacity - 1u;
-    uint32_t s = static_cast<uint32_t>((d[1] ^ (d[0] >> 17)) & mask);
+    uint32_t s = dedup_home(d, mask);
     for (;;) {
         const uint64_t cur = t.tags[s];
         if (cur == 0) { exists[i] = 0; return; }
-        if (cur == tag) {
-            const uint64_t* k = t.keys + 4ull * s;
-            if (k[0] == d[0] && k[1] == d[1] && k[2] == d[2] && k[3] == d[3]) { exists[i] = 1; return; }
-        }
+        if (cur == tag && same_key(t.keys + 4ull * s, d)) { exists[i] = 1; return; }
         s = (s + 1u) & mask;
     }
 }
@@ -116,12 +141,13 @@ __global__ __launch_bounds__(256) void dedup_rehash_kernel(DedupTable old_t, Ded
     const uint64_t* d = old_t.keys + 4ull * s0;
     const uint64_t tag = old_t.tags[s0];
     const uint32_t mask = new_t.capacity - 1u;
-    uint32_t s = static_cast<uint32_t>((d[1] ^ (d[0] >> 17)) & mask);
+    uint32_t s = dedup_home(d, mask);
     for (;;) {
         unsigned long long* tp = reinterpret_cast<unsigned long long*>(&new_t.tags[s]);
         if (atomicCAS(tp, 0ull, static_cast<unsigned long long>(tag)) == 0ull) {
             uint64_t* k = new_t.keys + 4ull * s;
             k[0] = d[0]; k[1] = d[1]; k[2] = d[2]; k[3] = d[3];
+            new_t.state[s] = kSlotSettled;
             return;
         }
         s = (s + 1u) & mask;
@@ -151,12 +177,13 @@ hipError_t launch_dedup_round(hipStream_t st, const DedupTable& t, const uint64_
                               uint8_t* pending, uint32_t* probe_start, uint32_t* slot_of, uint8_t* is_new,
                               unsigned int* n_unresolved, int first_round) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(dedup_claim_kernel, g1(n), dim3(256), 0, st, t, digests, n, pending, probe_start, slot_of, first_round);
+    hipLaunchKernelGGL(dedup_claim_kernel, g1(n), dim3(256), 0, st, t, digests, n, pending, probe_start, slot_of, is_new,
+                       first_round);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(dedup_write_kernel, g1(n), dim3(256), 0, st, t, digests, n, pending, slot_of, first_round);
+    hipLaunchKernelGGL(dedup_write_kernel, g1(n), dim3(256), 0, st, t, digests, n, pending, slot_of);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(dedup_verify_kernel, g1(n), dim3(256), 0, st, t, digests, n, pending, probe_start, slot_of,
-                       is_new, n_unresolved, first_round);
+                       is_new, n_unresolved);
     LAUNCH_CHECK();
     return hipSuccess;
 }

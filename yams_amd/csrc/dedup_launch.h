@@ -4,11 +4,16 @@
 
 namespace yams_accel {
 
+// DedupTable::state of a slot
+constexpr uint8_t kSlotUnwritten = 0; // no key: empty, or claimed in the running round
+constexpr uint8_t kSlotNew = 1;       // key written by the running batch (in this or an earlier round)
+constexpr uint8_t kSlotSettled = 2;   // key written by an earlier batch (or moved there by a rehash)
+
 struct DedupTable {
     uint64_t* tags;   // [capacity] first 8 digest bytes (0 = empty slot)
     uint64_t* keys;   // [capacity][4] full digests
-    uint32_t* owner;  // [capacity] lowest input index that touched the slot in the running batch
-    uint8_t* fresh;   // [capacity] 1 = claimed by the running batch
+    uint32_t* owner;  // [capacity] lowest input index that claimed the slot in the running batch
+    uint8_t* state;   // [capacity] kSlot*
     uint32_t capacity; // power of two
 };
 
