@@ -621,6 +621,73 @@ YAMS_ACCEL_API yams_status_t yams_scan_doc_topk_device(
     yams_scan_diag_t* diag);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Entity-vector search: IEntityStore::searchEntities over a mirror of entity_vectors           */
+/* ------------------------------------------------------------------------------------------ */
+/* SqliteVecBackend::Impl::searchEntities (src/vector/sqlite_vec_backend.cpp:2801-2887; seam
+ * include/yams/vector/entity_store.h:17-39; types vector_types.h:68, 140-177): the brute-force cosine search over the
+ * entity_vectors table (one embedding per symbol / node of the knowledge graph), called once per query by the hybrid
+ * search pipeline (src/search/search_vector_pipeline.cpp:439).  The corpus view is the mirror of the rows of
+ * entity_vectors whose embedding has `dim` floats, in rowid order; the attribute columns below stand next to it and the
+ * `WHERE embedding_type = ? AND node_type = ? AND document_hash = ?` predicate is evaluated on the device, per row and
+ * query.  Tombstones and other host-side restrictions use the view's row_mask. */
+#define YAMS_SCAN_ENTITY_UNSET 0xffffffffu  /* row_node_type / row_doc: no value; equals no filter value          */
+#define YAMS_SCAN_ENTITY_TYPE_UNSET 0xffu   /* row_type: no value; equals no filter value                         */
+typedef struct yams_scan_entities_s {
+    const uint8_t* row_type;       /* device [n_rows], nullable: EntityEmbeddingType ordinal (vector_types.h:68)     */
+    const uint32_t* row_node_type; /* device [n_rows], nullable: id the host interned for the node_type string       */
+    const uint32_t* row_doc;       /* device [n_rows], nullable: id the host interned for the document_hash string   */
+} yams_scan_entities_t;
+
+#define YAMS_SCAN_ENTITY_FILTER_TYPE 1u      /* AND embedding_type = ? (:2821-2823) */
+#define YAMS_SCAN_ENTITY_FILTER_NODE_TYPE 2u /* AND node_type = ?      (:2824-2826) */
+#define YAMS_SCAN_ENTITY_FILTER_DOC 4u       /* AND document_hash = ?  (:2827-2829) */
+typedef struct yams_scan_entity_filter_s { /* EntitySearchParams' three optional fields, one per query */
+    uint32_t fields;         /* YAMS_SCAN_ENTITY_FILTER_* bits: which of the values below take part                 */
+    uint32_t embedding_type; /* ids are opaque: a value no row carries (the UNSET values included) matches nothing  */
+    uint32_t node_type;
+    uint32_t doc;
+} yams_scan_entity_filter_t;
+
+/* Per query, the reference's contract (:2809-2884):
+ *   rows      those the query's filter and the view's row_mask admit, in row order;
+ *   score     float(computeCosineSimilarity(query, row)) (vector_database.cpp:1786-1810): dot, |q|^2, |row|^2 summed in
+ *             fp64 element by element, sqrt of each norm, 0.0 if either norm == 0.0 (tested BEFORE the division: a zero
+ *             query scores 0.0 against a NaN row, a zero row 0.0 against any query), else dot / (|q| * |row|).  No
+ *             finiteness test and no small-norm drop;
+ *   kept      iff score >= similarity_threshold (float compare: a NaN score or threshold keeps nothing);
+ *   order     score descending, the first min(k, kept).
+ * ZERO, NaN AND INFINITE QUERIES ARE SERVED, not refused: searchEntities validates nothing but emptiness (:2809-2811).
+ * That is the difference from every other search entry of this header, which drop zero-norm / non-finite rows and
+ * fail such queries.
+ * The reference sorts with std::sort on the score alone (:2873-2874), which is not stable: the order inside a run of
+ * equal scores (-0.0f == +0.0f), and which members of a run that straddles position k come back, the reference leaves
+ * open; this is the rule served: (score descending with -0.0 == +0.0, then row ordinal ascending) — what a stable
+ * sort of the table order gives, one of the reference's admissible outcomes.  Every returned score carries its own
+ * bits (a -0.0f stays -0.0f).
+ *   queries       device [n_queries][dim], raw
+ *   filters       HOST [n_queries], nullable (= no query has a filter); copied by the call
+ *   out_scores    device [n_queries][k] fp32, best first; unused slots hold -inf
+ *   out_rows      device [n_queries][k] int64: row_base + row ordinal; unused -1
+ *   out_counts    device [n_queries] uint32: rows returned
+ *   out_matching  device [n_queries] uint64, nullable: rows kept by the threshold (before the cut to k)
+ * k == 0: empty results (counts 0, nothing else written).  dim == 0 (the empty query, :2809-2811) or n_rows == 0: empty
+ * results, padded.  k <= YAMS_SCAN_MAX_K.
+ * The view's tie_rank / rank_row and filter shadows are IGNORED (the order has no secondary key but the row ordinal; every
+ * admitted row is scored in fp64).  With a row_mask, row_mask_count MUST equal the number of set bits (it bounds the list of
+ * admitted rows; a smaller value cuts that list at an arbitrary place).  A striped shard: YAMS_ERR_UNSUPPORTED.  An attribute id that no row carries is not
+ * an error; a filter that carries an unknown field bit, or names a field whose column is NULL while there are rows to
+ * describe, is YAMS_ERR_INVALID_ARG (over an empty table or an empty mask the result is empty whatever the filters name).
+ * Diagnostics: used_exact_scan = 1, path = 1, rows_visited = exact_distance_evaluations = rows that passed predicate and
+ * mask, returned_rows = rows kept by the threshold, both summed over the queries.
+ * Any batch size: the keys (8 bytes per query and admitted row) are processed in slices of queries that keep them within
+ * 256 MiB.  The call synchronises the context's stream before returning. */
+YAMS_ACCEL_API yams_status_t yams_scan_entity_topk_device(
+    yams_accel_ctx* ctx, const yams_scan_corpus_t* corpus, const yams_scan_entities_t* entities,
+    const float* queries, const yams_scan_entity_filter_t* filters, uint32_t n_queries, uint32_t k,
+    float similarity_threshold, float* out_scores, int64_t* out_rows, uint32_t* out_counts,
+    uint64_t* out_matching, yams_scan_diag_t* diag);
+
+/* ------------------------------------------------------------------------------------------ */
 /* SHA-256                                                                                      */
 /* ------------------------------------------------------------------------------------------ */
 /* Digest n_msgs byte ranges of one device buffer: message i = data[offsets[i] .. +lengths[i]).
@@ -919,6 +986,30 @@ typedef struct yams_vector_doc_scan_v1 {
                                  uint32_t** out_counts, uint64_t* out_matching, yams_scan_diag_t* out_diag);
     void (*free_doc_hits)(void* self, yams_scan_hit_t* hits, uint32_t* counts);
 } yams_vector_doc_scan_v1;
+
+/* IEntityStore::searchEntities over a vector_scan_v1 corpus (yams_scan_entity_topk_device): an entity table is its own
+ * corpus id, one per embedding dimension.  A separate interface, version 1, served by yams_plugin_get_interface and NOT
+ * listed in the manifest, for the reason given at vector_doc_scan_v1.  Host memory in, host memory out. */
+#define YAMS_IFACE_VECTOR_ENTITY_SCAN_V1 "vector_entity_scan_v1"
+#define YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION 1u
+typedef struct yams_vector_entity_scan_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION */
+    void* self;
+    /* The attribute columns of rows [first_row, first_row + n_rows) of the corpus (host arrays, each nullable = leave that
+     * column of the range as it is): EntityEmbeddingType ordinals, interned node_type ids, interned document_hash ids.
+     * Rows never set carry YAMS_SCAN_ENTITY_TYPE_UNSET / YAMS_SCAN_ENTITY_UNSET, which no filter matches; corpus_clear
+     * drops the columns.  A corpus dealt to several devices: YAMS_ERR_UNSUPPORTED. */
+    yams_status_t (*corpus_set_attributes)(void* self, uint64_t corpus_id, uint64_t first_row, uint64_t n_rows,
+                                           const uint8_t* types, const uint32_t* node_types, const uint32_t* docs);
+    /* searchEntities for n_queries queries: filters [n_queries] nullable, row_mask (host, nullable) as
+     * search_batch_masked (the adapter's tombstones).  hits [n_queries][k] with distance = 1 - similarity, counts
+     * [n_queries], out_matching (host [n_queries], nullable) = rows kept by the threshold.  Release with free_entity_hits. */
+    yams_status_t (*search_entities)(void* self, uint64_t corpus_id, const float* queries,
+                                     const yams_scan_entity_filter_t* filters, uint32_t n_queries, uint32_t dim, uint32_t k,
+                                     float similarity_threshold, const uint32_t* row_mask, yams_scan_hit_t** out_hits,
+                                     uint32_t** out_counts, uint64_t* out_matching, yams_scan_diag_t* out_diag);
+    void (*free_entity_hits)(void* self, yams_scan_hit_t* hits, uint32_t* counts);
+} yams_vector_entity_scan_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

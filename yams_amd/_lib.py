@@ -85,6 +85,18 @@ class ScanDocs(C.Structure):        # yams_scan_docs_t
 NO_DOC = 0xFFFFFFFF                 # YAMS_SCAN_NO_DOC
 
 
+class ScanEntities(C.Structure):    # yams_scan_entities_t
+    _fields_ = [("row_type", vp), ("row_node_type", vp), ("row_doc", vp)]
+
+
+class EntityFilter(C.Structure):    # yams_scan_entity_filter_t
+    _fields_ = [("fields", C.c_uint32), ("embedding_type", C.c_uint32), ("node_type", C.c_uint32), ("doc", C.c_uint32)]
+
+
+ENTITY_UNSET, ENTITY_TYPE_UNSET = 0xFFFFFFFF, 0xFF      # YAMS_SCAN_ENTITY_UNSET / _TYPE_UNSET
+ENTITY_FILTER_TYPE, ENTITY_FILTER_NODE_TYPE, ENTITY_FILTER_DOC = 1, 2, 4
+
+
 class ScanPqParams(C.Structure):    # yams_scan_pq_params_t
     _fields_ = [("k", C.c_uint32), ("similarity_threshold", C.c_float), ("rerank_factor", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -169,6 +181,17 @@ class VectorDocScanV1(C.Structure):  # vector_doc_scan_v1 (served by get_interfa
     ]
 
 
+class VectorEntityScanV1(C.Structure):  # vector_entity_scan_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("corpus_set_attributes", C.CFUNCTYPE(ST, vp, C.c_uint64, C.c_uint64, C.c_uint64, u8p, u32p, u32p)),
+        ("search_entities", C.CFUNCTYPE(ST, vp, C.c_uint64, f32p, C.POINTER(EntityFilter), C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_float, u32p, C.POINTER(C.POINTER(ScanHit)), C.POINTER(u32p), u64p,
+                                        C.POINTER(ScanDiag))),
+        ("free_entity_hits", C.CFUNCTYPE(None, vp, C.POINTER(ScanHit), u32p)),
+    ]
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -222,7 +245,7 @@ EXPORTS = [
     "yams_accel_download", "yams_accel_last_kernel_ms", "yams_accel_enable_kernel_timing",
     "yams_accel_debug_fail_alloc_after", "yams_accel_debug_alloc_faults", "yams_accel_debug_alloc_injection_compiled",
     "yams_scan_topk_device", "yams_scan_topk_host", "yams_scan_merge_topk_device", "yams_scan_pq_topk_device",
-    "yams_scan_doc_topk_device",
+    "yams_scan_doc_topk_device", "yams_scan_entity_topk_device",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -307,6 +330,8 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
                                            vp, C.c_uint64, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_doc_topk_device.argtypes = [vp, C.POINTER(ScanCorpus), C.POINTER(ScanDocs), vp, C.c_uint32, C.POINTER(ScanParams),
                                             vp, vp, vp, vp, vp, C.POINTER(ScanDiag)]
+    L.yams_scan_entity_topk_device.argtypes = [vp, C.POINTER(ScanCorpus), C.POINTER(ScanEntities), vp, C.POINTER(EntityFilter),
+                                               C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

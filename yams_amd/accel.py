@@ -441,6 +441,47 @@ class Accel:
         r.matching = matching
         return r
 
+    def entities_view(self, row_type_ptr: int | None = None, row_node_type_ptr: int | None = None,
+                      row_doc_ptr: int | None = None) -> "_lib.ScanEntities":
+        """yams_scan_entities_t over device columns: row_type u8 [n_rows], row_node_type / row_doc u32 [n_rows] (each or None)."""
+        return _lib.ScanEntities(row_type_ptr, row_node_type_ptr, row_doc_ptr)
+
+    def scan_entity_topk(self, corpus: ScanCorpus, entities, queries: np.ndarray, k: int, threshold: float = 0.5,
+                         filters=None) -> ScanResult:
+        """IEntityStore::searchEntities on the device (yams_scan_entity_topk_device) from host queries.  filters: None, or one
+        (embedding_type | None, node_type id | None, document id | None) per query.  The result's `matching` holds the rows
+        kept by the threshold; zero / NaN / inf queries are served."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        kk = max(k, 1)
+        fl = None
+        if filters is not None:
+            assert len(filters) == nq
+            fl = (_lib.EntityFilter * max(nq, 1))()
+            for i, (t, nt, d) in enumerate(filters):
+                fl[i] = _lib.EntityFilter((_lib.ENTITY_FILTER_TYPE if t is not None else 0) | (_lib.ENTITY_FILTER_NODE_TYPE if nt is not None else 0) |
+                                          (_lib.ENTITY_FILTER_DOC if d is not None else 0), t or 0, nt or 0, d or 0)
+        d_q = self.to_device(q) if q.size else None
+        d_s = self.alloc(nq * kk * 4 + 16); d_r = self.alloc(nq * kk * 8 + 16)
+        d_n = self.alloc(nq * 4 + 16); d_m = self.alloc(nq * 8 + 16)
+        try:
+            diag = ScanDiag()
+            self._check(self.L.yams_scan_entity_topk_device(self.ctx, C.byref(corpus), C.byref(entities), d_q.ptr if d_q else None, fl, nq,
+                                                            k, threshold, d_s.ptr, d_r.ptr, d_n.ptr, d_m.ptr, C.byref(diag)))
+            counts = d_n.download(np.uint32, nq)
+            scores = d_s.download(np.float32, nq * kk).reshape(nq, kk)[:, :k]
+            rows = d_r.download(np.int64, nq * kk).reshape(nq, kk)[:, :k]
+            matching = d_m.download(np.uint64, nq)
+        finally:
+            for b in (d_q, d_s, d_r, d_n, d_m):
+                if b is not None:
+                    b.free()
+        r = ScanResult(scores, rows, counts, None, diag.as_dict())
+        r.matching = matching
+        return r
+
     def scan_pq_topk(self, corpus: ScanCorpus, codes: np.ndarray, luts: np.ndarray, queries: np.ndarray, k: int, threshold: float = -1.0,
                      rerank_factor: int = 2, tie_keys: np.ndarray | None = None, row_of_index: np.ndarray | None = None,
                      candidates: np.ndarray | None = None, sum_lanes: int = 1) -> ScanResult:

@@ -1,0 +1,308 @@
+// entity_kernels.hip — gfx950 kernels of the entity-vector search (IEntityStore::searchEntities).
+//
+// Reference semantics being reproduced (paths relative to the reference checkout):
+//   src/vector/sqlite_vec_backend.cpp:2801-2887   searchEntities: entity_vectors WHERE [embedding_type = ?] [AND node_type = ?]
+//                                                 [AND document_hash = ?] in table order, similarity = float(cosine),
+//                                                 kept iff similarity >= threshold, std::sort by similarity desc, first k
+//   src/vector/vector_database.cpp:1786-1810      computeCosineSimilarity: dot, norm_a, norm_b summed in fp64, element by
+//                                                 element; 0.0 if either norm == 0.0 (tested BEFORE the division); no
+//                                                 finiteness test, no small-norm drop, no query validation
+// std::sort has one key and is not stable: the order inside a run of equal similarities (-0.0f == +0.0f) is left open by the
+// reference; the rule served here is (similarity desc, row ordinal asc) — what a stable sort of the table order gives.
+//
+// Launches per call:
+//   entity_qnorm_kernel     sqrt of the fp64 sum of squares of every query, in element order
+//   entity_compact_kernel   only when a row_mask or the filters restrict the rows: the ordinals some query admits
+//   per slice of queries:
+//   entity_score_kernel     every admitted row is read from HBM once per group of QG queries (128-byte row chunks staged
+//                           through LDS with 16-byte loads, the next chunk's loads in flight while this one is summed),
+//                           scored, counted, and its key pack_key(similarity with -0.0 -> +0.0, row) written
+//   topk_multilevel + entity_emit_kernel   the k best keys of each query and their rows; a winner whose similarity is a
+//                           zero is scored again for the sign of its zero (the key holds the canonical one)
+#include <algorithm>
+
+#include "common.h"
+
+namespace yams_accel {
+
+namespace {
+
+constexpr int kEntThreads = 256;        // rows per workgroup (one per thread)
+constexpr int kEntChunk = 32;           // elements of a row per LDS stage (128 bytes)
+constexpr int kEntLds = kEntChunk + 1;  // padded LDS row stride (floats): thread t reads row t, conflict-free
+constexpr int kEntLoads = kEntChunk / 4; // 16-byte loads per thread and stage: 8 lanes per row, 32 rows per pass, 8 passes
+
+// The predicate of one query over the attribute columns (three optional column equalities).  The "unset" value of a
+// column equals no filter value; a null column behind a named field never gets here (the host refuses the call).
+__device__ __forceinline__ bool entity_admits(const yams_scan_entity_filter_t& f, const uint8_t* row_type,
+                                              const uint32_t* row_node_type, const uint32_t* row_doc, uint64_t row) {
+    if ((f.fields & YAMS_SCAN_ENTITY_FILTER_TYPE) && !(f.embedding_type < YAMS_SCAN_ENTITY_TYPE_UNSET && row_type[row] == f.embedding_type)) return false;
+    if ((f.fields & YAMS_SCAN_ENTITY_FILTER_NODE_TYPE) && !(f.node_type != YAMS_SCAN_ENTITY_UNSET && row_node_type[row] == f.node_type)) return false;
+    if ((f.fields & YAMS_SCAN_ENTITY_FILTER_DOC) && !(f.doc != YAMS_SCAN_ENTITY_UNSET && row_doc[row] == f.doc)) return false;
+    return true;
+}
+
+// computeCosineSimilarity's tail (:1802-1809) and the cast of :2859: nsq = the row's sum of squares, qn = sqrt of the query's.
+__device__ __forceinline__ float entity_similarity(double dot, double nsq, double qn) {
+    const double rn = sqrt(nsq);
+    const double sd = (qn == 0.0 || rn == 0.0) ? 0.0 : dot / (qn * rn);
+    return static_cast<float>(sd);
+}
+
+// up to four consecutive floats of a row (zero-filled past `left`), as one 16-byte load when the layout allows it
+__device__ __forceinline__ float4 entity_load4(const float* src, uint32_t left, int vec4) {
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (vec4 && left >= 4) {
+        x = *reinterpret_cast<const float4*>(src);
+    } else {
+        if (left > 0) x.x = src[0];
+        if (left > 1) x.y = src[1];
+        if (left > 2) x.z = src[2];
+        if (left > 3) x.w = src[3];
+    }
+    return x;
+}
+
+} // namespace
+
+// qnorm[q] = sqrt(sum of squares), fp64, element by element (norm_a of :1798,1802).  One thread per query.
+__global__ __launch_bounds__(64) void entity_qnorm_kernel(const float* __restrict__ queries, uint32_t nq, uint32_t dim,
+                                                          double* __restrict__ qnorm) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const float* x = queries + static_cast<uint64_t>(q) * dim;
+    double s = 0.0;
+    for (uint32_t i = 0; i < dim; ++i) {
+        const double v = static_cast<double>(x[i]);
+        s = fma(v, v, s);
+    }
+    qnorm[q] = sqrt(s);
+}
+
+// Row ordinals that the row_mask (nullable) lets through and that at least one of the call's distinct filters admits
+// (n_filters == 0: the filters do not restrict).  Any order: the keys carry the ordinal.
+__global__ __launch_bounds__(256) void entity_compact_kernel(const uint32_t* __restrict__ row_mask, uint64_t n_rows,
+                                                             const yams_scan_entity_filter_t* __restrict__ filters,
+                                                             uint32_t n_filters, const uint8_t* __restrict__ row_type,
+                                                             const uint32_t* __restrict__ row_node_type,
+                                                             const uint32_t* __restrict__ row_doc, uint32_t* rows_sel,
+                                                             unsigned long long* counter) {
+    const uint64_t row = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    bool on = row < n_rows && (!row_mask || ((row_mask[row >> 5] >> (row & 31)) & 1u));
+    if (on && n_filters) {
+        bool any = false;
+        for (uint32_t f = 0; f < n_filters && !any; ++f) any = entity_admits(filters[f], row_type, row_node_type, row_doc, row);
+        on = any;
+    }
+    const unsigned long long ball = __ballot(on);
+    if (ball == 0) return;
+    const int lane = threadIdx.x & 63;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(counter, static_cast<unsigned long long>(__popcll(ball)));
+    base = __shfl(base, 0);
+    if (on) rows_sel[base + __popcll(ball & ((1ull << lane) - 1ull))] = static_cast<uint32_t>(row);
+}
+
+// One thread per item (rows_sel: the compacted ordinals, bounded by *n_sel_dev; else item == row), QG queries per workgroup
+// (blockIdx.y * QG + j of the slice).  keys[slot][item] for every item < n_items: 0 = not kept.
+template <int QG>
+__global__ __launch_bounds__(kEntThreads) void entity_score_kernel(
+    const float* __restrict__ rows, uint64_t n_rows, uint32_t dim, int vec4, const float* __restrict__ queries,
+    const double* __restrict__ qnorm, const yams_scan_entity_filter_t* __restrict__ filters, uint32_t q0, uint32_t n_slots,
+    const uint8_t* __restrict__ row_type, const uint32_t* __restrict__ row_node_type, const uint32_t* __restrict__ row_doc,
+    const uint32_t* __restrict__ rows_sel, const unsigned long long* n_sel_dev, uint64_t n_items, float threshold,
+    unsigned long long* __restrict__ keys, unsigned long long* visited, unsigned long long* matching) {
+    __shared__ float s_rows[kEntThreads * kEntLds];
+    __shared__ float s_q[QG][kEntChunk];
+    __shared__ uint32_t s_row[kEntThreads];
+    __shared__ uint32_t s_count[2][QG];
+    const int t = threadIdx.x, lane = t & 63;
+    const uint32_t slot0 = blockIdx.y * QG;
+    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kEntThreads + t;
+    const uint64_t n_valid = rows_sel ? (*n_sel_dev < n_items ? *n_sel_dev : n_items) : n_items;
+    if (static_cast<uint64_t>(blockIdx.x) * kEntThreads >= n_valid) { // (a compacted list shorter than its bound: empty keys)
+        if (item < n_items) {
+#pragma unroll
+            for (int j = 0; j < QG; ++j)
+                if (slot0 + j < n_slots) keys[static_cast<uint64_t>(slot0 + j) * n_items + item] = 0ull;
+        }
+        return;
+    }
+    uint64_t row = 0;
+    bool in = item < n_valid;
+    if (in) {
+        row = rows_sel ? rows_sel[item] : item;
+        if (row >= n_rows) in = false;
+    }
+    // which queries of the group admit the row (the row_mask has been applied by the compaction)
+    uint32_t adm = 0;
+#pragma unroll
+    for (int j = 0; j < QG; ++j) {
+        const uint32_t slot = slot0 + j;
+        if (in && slot < n_slots && (!filters || entity_admits(filters[q0 + slot], row_type, row_node_type, row_doc, row))) adm |= 1u << j;
+    }
+    const bool on = adm != 0; // a row that no query of the group admits is never read
+    s_row[t] = on ? static_cast<uint32_t>(row) : 0xffffffffu;
+    if (t < 2 * QG) s_count[t / QG][t % QG] = 0;
+    __syncthreads();
+
+    // stage geometry: 8 lanes per row, 16 bytes each -> a wave loads 8 rows x 128 contiguous bytes per instruction
+    const int v = (t & 7) * 4;
+    const float* src[kEntLoads];
+#pragma unroll
+    for (int it = 0; it < kEntLoads; ++it) {
+        const uint32_t r = s_row[it * (kEntThreads / 8) + (t >> 3)];
+        src[it] = r != 0xffffffffu ? rows + static_cast<uint64_t>(r) * dim + v : nullptr;
+    }
+    float4 pre[kEntLoads];
+    auto fetch = [&](uint32_t c0) {
+        const uint32_t cl = dim - c0 < static_cast<uint32_t>(kEntChunk) ? dim - c0 : static_cast<uint32_t>(kEntChunk);
+        const uint32_t left = static_cast<uint32_t>(v) < cl ? cl - v : 0u;
+#pragma unroll
+        for (int it = 0; it < kEntLoads; ++it)
+            pre[it] = (src[it] && left) ? entity_load4(src[it] + c0, left, vec4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    fetch(0);
+
+    double nsq = 0.0, dot[QG];
+#pragma unroll
+    for (int j = 0; j < QG; ++j) dot[j] = 0.0;
+    for (uint32_t c0 = 0; c0 < dim; c0 += kEntChunk) {
+        const uint32_t cl = dim - c0 < static_cast<uint32_t>(kEntChunk) ? dim - c0 : static_cast<uint32_t>(kEntChunk);
+#pragma unroll
+        for (int it = 0; it < kEntLoads; ++it) {
+            float* dst = s_rows + (it * (kEntThreads / 8) + (t >> 3)) * kEntLds + v;
+            dst[0] = pre[it].x; dst[1] = pre[it].y; dst[2] = pre[it].z; dst[3] = pre[it].w;
+        }
+        for (int i = t; i < QG * kEntChunk; i += kEntThreads) {
+            const int j = i / kEntChunk, e = i % kEntChunk;
+            const uint32_t slot = slot0 + j;
+            s_q[j][e] = (slot < n_slots && static_cast<uint32_t>(e) < cl)
+                            ? queries[static_cast<uint64_t>(q0 + slot) * dim + c0 + e] : 0.f;
+        }
+        __syncthreads();
+        // the next chunk's loads are issued before this chunk's fp64 chain and land in registers while it runs
+        if (c0 + kEntChunk < dim) fetch(c0 + kEntChunk);
+        if (on) {
+            const float* x = s_rows + t * kEntLds;
+            // the reference's order: one sequential chain per sum, element by element (:1796-1800); a product of two
+            // floats is exact in fp64, so fma == multiply then add
+#pragma unroll 4
+            for (uint32_t i = 0; i < cl; ++i) {
+                const double sv = static_cast<double>(x[i]);
+                nsq = fma(sv, sv, nsq);
+#pragma unroll
+                for (int j = 0; j < QG; ++j) dot[j] = fma(static_cast<double>(s_q[j][i]), sv, dot[j]);
+            }
+        }
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int j = 0; j < QG; ++j) {
+        const uint32_t slot = slot0 + j;
+        unsigned long long key = 0;
+        const bool a = (adm >> j) & 1u;
+        if (a) {
+            const float sim = entity_similarity(dot[j], nsq, qnorm[q0 + slot]);
+            // float compare (:2862): a NaN similarity or threshold keeps nothing; -0.0f and +0.0f are one score
+            if (sim >= threshold) key = pack_key(sim == 0.0f ? 0.0f : sim, static_cast<uint32_t>(row));
+        }
+        if (slot < n_slots && item < n_items) keys[static_cast<uint64_t>(slot) * n_items + item] = key;
+        const unsigned long long ball_a = __ballot(a), ball_k = __ballot(key != 0);
+        if (lane == 0 && ball_a) atomicAdd(&s_count[0][j], static_cast<uint32_t>(__popcll(ball_a)));
+        if (lane == 0 && ball_k) atomicAdd(&s_count[1][j], static_cast<uint32_t>(__popcll(ball_k)));
+    }
+    __syncthreads();
+    if (t < QG && slot0 + t < n_slots) {
+        if (s_count[0][t]) atomicAdd(visited + q0 + slot0 + t, static_cast<unsigned long long>(s_count[0][t]));
+        if (s_count[1][t]) atomicAdd(matching + q0 + slot0 + t, static_cast<unsigned long long>(s_count[1][t]));
+    }
+}
+
+// The k winners of every slot: score, row (row_base + ordinal), count; unused slots -inf / -1.  The key of a winner whose
+// similarity is a zero holds +0.0: its own bits (the reference returns -0.0f where the quotient underflows from below) come
+// from scoring the row again with the same chains.
+__global__ __launch_bounds__(256) void entity_emit_kernel(const unsigned long long* res, uint64_t res_stride,
+                                                          const float* __restrict__ rows, uint32_t dim,
+                                                          const float* __restrict__ queries, const double* __restrict__ qnorm,
+                                                          int64_t row_base, uint32_t q0, uint32_t k, float* out_scores,
+                                                          int64_t* out_rows, uint32_t* out_counts) {
+    const uint32_t slot = blockIdx.x;
+    const uint32_t q = q0 + slot;
+    __shared__ uint32_t s_n;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < k; i += blockDim.x) {
+        const uint64_t o = static_cast<uint64_t>(q) * k + i;
+        const unsigned long long s = res ? res[static_cast<uint64_t>(slot) * res_stride + i] : 0ull;
+        if (s) {
+            const uint32_t r = key_idx(s);
+            float sim = key_score(s);
+            if (sim == 0.0f) {
+                const float* x = rows + static_cast<uint64_t>(r) * dim;
+                const float* y = queries + static_cast<uint64_t>(q) * dim;
+                double nsq = 0.0, dot = 0.0;
+                for (uint32_t e = 0; e < dim; ++e) {
+                    const double sv = static_cast<double>(x[e]);
+                    nsq = fma(sv, sv, nsq);
+                    dot = fma(static_cast<double>(y[e]), sv, dot);
+                }
+                sim = entity_similarity(dot, nsq, qnorm[q]);
+            }
+            out_scores[o] = sim;
+            out_rows[o] = row_base + static_cast<int64_t>(r);
+            atomicAdd(&s_n, 1u);
+        } else {
+            out_scores[o] = -__builtin_inff();
+            out_rows[o] = -1;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) out_counts[q] = s_n; // (the winners are a prefix: keys are sorted, 0-padded)
+}
+
+hipError_t launch_entity_qnorm(hipStream_t st, const float* queries, uint32_t nq, uint32_t dim, double* qnorm) {
+    if (nq == 0) return hipSuccess;
+    hipLaunchKernelGGL(entity_qnorm_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, queries, nq, dim, qnorm);
+    return hipGetLastError();
+}
+
+hipError_t launch_entity_compact(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows,
+                                 const yams_scan_entity_filter_t* filters, uint32_t n_filters,
+                                 const yams_scan_entities_t& cols, uint32_t* rows_sel, unsigned long long* counter) {
+    if (n_rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(entity_compact_kernel, dim3(static_cast<uint32_t>((n_rows + 255) / 256)), dim3(256), 0, st, row_mask,
+                       n_rows, filters, n_filters, cols.row_type, cols.row_node_type, cols.row_doc, rows_sel, counter);
+    return hipGetLastError();
+}
+
+hipError_t launch_entity_score(hipStream_t st, const float* rows, uint64_t n_rows, uint32_t dim, const float* queries,
+                               const double* qnorm, const yams_scan_entity_filter_t* filters, uint32_t q0, uint32_t n_slots,
+                               const yams_scan_entities_t& cols, const uint32_t* rows_sel, const unsigned long long* n_sel_dev,
+                               uint64_t n_items, float threshold, unsigned long long* keys, unsigned long long* visited,
+                               unsigned long long* matching) {
+    if (n_items == 0 || n_slots == 0) return hipSuccess;
+    const int vec4 = ((reinterpret_cast<uintptr_t>(rows) & 15u) == 0 && (dim & 3u) == 0) ? 1 : 0;
+    const uint32_t gx = static_cast<uint32_t>((n_items + kEntThreads - 1) / kEntThreads);
+#define YAMS_ENTITY_SCORE(QG)                                                                                                  \
+    hipLaunchKernelGGL((entity_score_kernel<QG>), dim3(gx, (n_slots + QG - 1) / QG), dim3(kEntThreads), 0, st, rows, n_rows,  \
+                       dim, vec4, queries, qnorm, filters, q0, n_slots, cols.row_type, cols.row_node_type, cols.row_doc,      \
+                       rows_sel, n_sel_dev, n_items, threshold, keys, visited, matching)
+    if (n_slots == 1) YAMS_ENTITY_SCORE(1);
+    else if (n_slots <= 4) YAMS_ENTITY_SCORE(4);
+    else YAMS_ENTITY_SCORE(8);
+#undef YAMS_ENTITY_SCORE
+    return hipGetLastError();
+}
+
+hipError_t launch_entity_emit(hipStream_t st, const unsigned long long* res, uint64_t res_stride, const float* rows, uint32_t dim,
+                              const float* queries, const double* qnorm, int64_t row_base, uint32_t q0, uint32_t n_slots,
+                              uint32_t k, float* out_scores, int64_t* out_rows, uint32_t* out_counts) {
+    if (n_slots == 0) return hipSuccess;
+    hipLaunchKernelGGL(entity_emit_kernel, dim3(n_slots), dim3(256), 0, st, res, res_stride, rows, dim, queries, qnorm, row_base,
+                       q0, k, out_scores, out_rows, out_counts);
+    return hipGetLastError();
+}
+
+} // namespace yams_accel

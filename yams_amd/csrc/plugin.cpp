@@ -270,6 +270,25 @@ struct DocMap {
     }
 };
 
+// The attribute columns of an entity corpus (vector_entity_scan_v1.corpus_set_attributes), on the corpus's device.  The host
+// copies cover the rows set so far; rows appended later carry the "unset" values (padded per search).
+struct EntityCols {
+    std::vector<uint8_t> type; std::vector<uint32_t> node, doc;
+    uint8_t* d_type = nullptr; uint32_t* d_node = nullptr; uint32_t* d_doc = nullptr;
+    uint64_t n_rows = 0; int device = 0;
+    void release_device() {
+        if (d_type || d_node || d_doc) (void)hipSetDevice(device);
+        if (d_type) (void)hipFree(d_type);
+        if (d_node) (void)hipFree(d_node);
+        if (d_doc) (void)hipFree(d_doc);
+        d_type = nullptr; d_node = d_doc = nullptr;
+    }
+    void release() {
+        release_device(); n_rows = 0;
+        std::vector<uint8_t>().swap(type); std::vector<uint32_t>().swap(node); std::vector<uint32_t>().swap(doc);
+    }
+};
+
 struct Corpus {
     uint32_t dim = 0;
     uint64_t n_rows = 0;
@@ -277,6 +296,7 @@ struct Corpus {
     uint64_t i8_decided_rows = 0;    // rows the "auto" decision looked at (one taken from fewer than 4096 rows is taken again once they are there)
     PqIndex pq;                      // (version 2 of the vtable: pq_index_set / search_pq)
     DocMap docs;                     // (vector_doc_scan_v1)
+    EntityCols ents;                 // (vector_entity_scan_v1)
     std::vector<ShardStore> sh;      // one per plugin device
     GrowBuf rank_of_row;             // device 0: the corpus-wide chunk_id ranking (cross-shard ties)
     bool has_ranks = false;
@@ -689,6 +709,7 @@ yams_status_t vs_corpus_set_tie_ranks(void*, uint64_t id, const uint32_t* ranks,
 void release_corpus(Corpus& c) {
     c.pq.release();
     c.docs.release();
+    c.ents.release();
     for (auto& s : c.sh) s.release();
     c.rank_of_row.release();
     c.n_rows = 0; c.has_ranks = false; c.i8_flags = -1; c.i8_decided_rows = 0;
@@ -702,6 +723,7 @@ yams_status_t vs_corpus_clear(void*, uint64_t id) {
     std::unique_lock<std::shared_mutex> lk(c->mu);
     for (auto& s : c->sh) { s.n_rows = 0; s.has_tie = false; }
     c->docs.release();
+    c->ents.release();
     c->n_rows = 0; c->has_ranks = false; c->i8_flags = -1; c->i8_decided_rows = 0;
     return YAMS_OK;
 }
@@ -1046,6 +1068,122 @@ void ds_free_doc_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::fre
 
 yams_vector_doc_scan_v1 g_vector_doc_scan = {YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION, nullptr, GUARDED(ds_corpus_set_documents),
                                              GUARDED(ds_search_docs), GUARDED(ds_free_doc_hits)};
+
+// ---- vector_entity_scan_v1: IEntityStore::searchEntities over a vector_scan_v1 corpus (yams_scan_entity_topk_device) ---------
+yams_status_t es_corpus_set_attributes(void*, uint64_t id, uint64_t first_row, uint64_t n_rows, const uint8_t* types,
+                                       const uint32_t* node_types, const uint32_t* docs) {
+    NEED_INIT();
+    auto c = find_corpus(id);
+    if (!c) return YAMS_ERR_NOT_FOUND;
+    std::unique_lock<std::shared_mutex> lk(c->mu);
+    if (c->sh.size() != 1) return YAMS_ERR_UNSUPPORTED;      // (attribute columns over a striped corpus: not built)
+    if (first_row > c->n_rows || n_rows > c->n_rows - first_row) return YAMS_ERR_INVALID_ARG;
+    EntityCols& e = c->ents;
+    // rows never set carry the "unset" values
+    e.type.resize(c->n_rows, YAMS_SCAN_ENTITY_TYPE_UNSET);
+    e.node.resize(c->n_rows, YAMS_SCAN_ENTITY_UNSET);
+    e.doc.resize(c->n_rows, YAMS_SCAN_ENTITY_UNSET);
+    if (types) std::copy(types, types + n_rows, e.type.begin() + first_row);
+    if (node_types) std::copy(node_types, node_types + n_rows, e.node.begin() + first_row);
+    if (docs) std::copy(docs, docs + n_rows, e.doc.begin() + first_row);
+    e.release_device();
+    e.n_rows = 0; e.device = c->sh[0].device;
+    if (c->n_rows == 0) return YAMS_OK;
+    (void)hipSetDevice(e.device);
+    const size_t n = c->n_rows;
+    if (yams_accel::ya_malloc(reinterpret_cast<void**>(&e.d_type), n) != hipSuccess ||
+        yams_accel::ya_malloc(reinterpret_cast<void**>(&e.d_node), n * 4) != hipSuccess ||
+        yams_accel::ya_malloc(reinterpret_cast<void**>(&e.d_doc), n * 4) != hipSuccess) {
+        (void)hipGetLastError(); e.release_device();          // (the host copies stay: the next search pads from them)
+        return YAMS_ERR_RESOURCE_EXHAUSTED;
+    }
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    if (yams_accel_upload(w.v, e.d_type, e.type.data(), n) != YAMS_OK || yams_accel_upload(w.v, e.d_node, e.node.data(), n * 4) != YAMS_OK ||
+        yams_accel_upload(w.v, e.d_doc, e.doc.data(), n * 4) != YAMS_OK) { e.release_device(); return YAMS_ERR_INTERNAL; }
+    e.n_rows = n;
+    return YAMS_OK;
+}
+
+yams_status_t es_search_entities(void*, uint64_t id, const float* queries, const yams_scan_entity_filter_t* filters, uint32_t nq,
+                                 uint32_t dim, uint32_t k, float threshold, const uint32_t* row_mask_host, yams_scan_hit_t** out_hits,
+                                 uint32_t** out_counts, uint64_t* out_matching, yams_scan_diag_t* out_diag) {
+    NEED_INIT();
+    if (!out_hits || !out_counts) return YAMS_ERR_INVALID_ARG;
+    *out_hits = nullptr; *out_counts = nullptr;
+    if (k > YAMS_SCAN_MAX_K) return YAMS_ERR_UNSUPPORTED;
+    auto c = find_corpus(id);
+    if (!c) return YAMS_ERR_NOT_FOUND;
+    if (dim != c->dim) return YAMS_ERR_INVALID_ARG;           // (a row of another size is skipped, :2858: such rows live in another corpus)
+    if (nq && !queries) return YAMS_ERR_INVALID_ARG;
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    if (c->sh.size() != 1) return YAMS_ERR_UNSUPPORTED;
+    const ShardStore& s = c->sh[0];
+    const EntityCols& e = c->ents;
+    const size_t slots = static_cast<size_t>(nq) * std::max<uint32_t>(k, 1);
+    auto* counts = static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)));
+    auto* hits = static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)));
+    if (!counts || !hits) { std::free(counts); std::free(hits); return YAMS_ERR_INTERNAL; }
+    auto done = [&](yams_status_t st) { if (st != YAMS_OK) { std::free(counts); std::free(hits); } else { *out_hits = hits; *out_counts = counts; } return st; };
+    for (size_t o = 0; o < slots; ++o) hits[o].row = -1;
+    if (nq == 0) { if (out_diag) std::memset(out_diag, 0, sizeof *out_diag); return done(YAMS_OK); }
+    (void)hipSetDevice(s.device);
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    yams_accel_ctx* x = w.v;
+    float* d_q; float* d_s; int64_t* d_r; uint32_t* d_n; uint64_t* d_m;
+    yams_status_t st;
+    if ((st = yams_accel::ws_get(x, "plugin_ent_queries", static_cast<size_t>(nq) * dim * 4, (void**)&d_q)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_ent_scores", slots * 4, (void**)&d_s)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_ent_rows", slots * 8, (void**)&d_r)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_ent_counts", static_cast<size_t>(nq) * 4, (void**)&d_n)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_ent_matching", static_cast<size_t>(nq) * 8, (void**)&d_m)) != YAMS_OK) return done(st);
+    if (yams_accel_upload(x, d_q, queries, static_cast<size_t>(nq) * dim * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
+    yams_scan_corpus_t v;
+    std::memset(&v, 0, sizeof v);
+    v.rows = s.rows.as<float>(); v.n_rows = s.n_rows; v.dim = c->dim;
+    if (row_mask_host && s.n_rows) {   // tombstones / host-side restrictions
+        const size_t words = (s.n_rows + 31) / 32;
+        std::vector<uint32_t> mask(row_mask_host, row_mask_host + words);
+        if (s.n_rows % 32) mask.back() &= (1u << (s.n_rows % 32)) - 1u;
+        uint64_t bits = 0;
+        for (uint32_t m : mask) bits += static_cast<uint64_t>(__builtin_popcount(m));
+        uint32_t* d_mask;
+        if ((st = yams_accel::ws_get(x, "plugin_ent_mask", words * 4, (void**)&d_mask)) != YAMS_OK) return done(st);
+        if (yams_accel_upload(x, d_mask, mask.data(), words * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
+        v.row_mask = d_mask; v.row_mask_count = bits;
+    }
+    // the attribute columns; rows appended after they were last set carry the "unset" values
+    yams_scan_entities_t cols{e.d_type, e.d_node, e.d_doc};
+    if (s.n_rows > e.n_rows) {
+        const size_t n = s.n_rows;
+        std::vector<uint8_t> t(n, YAMS_SCAN_ENTITY_TYPE_UNSET); std::vector<uint32_t> nd(n, YAMS_SCAN_ENTITY_UNSET), dc(n, YAMS_SCAN_ENTITY_UNSET);
+        std::copy(e.type.begin(), e.type.end(), t.begin()); std::copy(e.node.begin(), e.node.end(), nd.begin());
+        std::copy(e.doc.begin(), e.doc.end(), dc.begin());
+        uint8_t* p;
+        const size_t off = (n + 15) & ~static_cast<size_t>(15);
+        if ((st = yams_accel::ws_get(x, "plugin_ent_cols", off + n * 8, (void**)&p)) != YAMS_OK) return done(st);
+        if (yams_accel_upload(x, p, t.data(), n) != YAMS_OK || yams_accel_upload(x, p + off, nd.data(), n * 4) != YAMS_OK ||
+            yams_accel_upload(x, p + off + n * 4, dc.data(), n * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
+        cols = yams_scan_entities_t{p, reinterpret_cast<uint32_t*>(p + off), reinterpret_cast<uint32_t*>(p + off + n * 4)};
+    }
+    if ((st = yams_scan_entity_topk_device(x, &v, &cols, d_q, filters, nq, k, threshold, d_s, d_r, d_n, d_m, out_diag)) != YAMS_OK) return done(st);
+    std::vector<float> scores(slots); std::vector<int64_t> rows(slots);
+    if (yams_accel_download(x, counts, d_n, static_cast<size_t>(nq) * 4) != YAMS_OK ||
+        (k && yams_accel_download(x, scores.data(), d_s, slots * 4) != YAMS_OK) ||
+        (k && yams_accel_download(x, rows.data(), d_r, slots * 8) != YAMS_OK) ||
+        (out_matching && yams_accel_download(x, out_matching, d_m, static_cast<size_t>(nq) * 8) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
+    for (uint32_t q = 0; q < nq; ++q)
+        for (uint32_t i = 0; i < k && i < counts[q]; ++i) {
+            const size_t o = static_cast<size_t>(q) * k + i;
+            hits[o].row = rows[o]; hits[o].similarity = scores[o]; hits[o].distance = 1.0f - scores[o];
+        }
+    ++g.searches;
+    return done(YAMS_OK);
+}
+
+void es_free_entity_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::free(hits); std::free(counts); }
+
+yams_vector_entity_scan_v1 g_vector_entity_scan = {YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION, nullptr, GUARDED(es_corpus_set_attributes),
+                                                   GUARDED(es_search_entities), GUARDED(es_free_entity_hits)};
 
 // ---- content_hash_v1 --------------------------------------------------------------------------
 // Every call leases one of the plugin's work contexts (own stream, own workspace), so hashing, chunking
@@ -1547,6 +1685,10 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
     if (std::strcmp(iface_id, YAMS_IFACE_VECTOR_DOC_SCAN_V1) == 0) { // (not in the manifest: see the header)
         if (version < 1 || version > YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
         *out_iface = &g_vector_doc_scan; return YAMS_PLUGIN_OK;
+    }
+    if (std::strcmp(iface_id, YAMS_IFACE_VECTOR_ENTITY_SCAN_V1) == 0) { // (not in the manifest: see the header)
+        if (version < 1 || version > YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
+        *out_iface = &g_vector_entity_scan; return YAMS_PLUGIN_OK;
     }
     if (std::strcmp(iface_id, YAMS_IFACE_CONTENT_HASH_V1) == 0) {
         if (version < 1 || version > YAMS_IFACE_CONTENT_HASH_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
