@@ -111,12 +111,10 @@ public:
             if (r.embedding.size() != dim_) return Error{ErrorCode::InvalidArgument, "embedding dimension mismatch"};
             for (float v : r.embedding) if (!std::isfinite(v)) return Error{ErrorCode::InvalidArgument, "non-finite embedding"};
         }
-        // chunk_ids repeated inside one batch: the last write wins (:1086-1226)
-        std::unordered_map<std::string, size_t> last;
-        for (size_t i = 0; i < records.size(); ++i) last[records[i].chunk_id] = i;
-        for (size_t i = 0; i < records.size(); ++i) {
+        // chunk_ids repeated inside one batch: the row takes the POSITION of the first occurrence and the CONTENT of the
+        // last (unique_indices, :1114-1130) — the vec0 engine returns equal distances in rowid order
+        for (size_t i : uniqueInBatch(records)) {
             const auto& r = records[i];
-            if (last[r.chunk_id] != i) continue;
             auto it = byId_.find(r.chunk_id);
             if (it != byId_.end()) kill(it->second);
             // rows appended in ascending chunk_id order need no rank table: row order IS the
@@ -126,12 +124,24 @@ public:
             byId_[r.chunk_id] = records_.size();
             byDoc_[r.document_hash].push_back(static_cast<uint32_t>(records_.size()));
             records_.push_back(r);
+            serial_.push_back(nextSerial_++);
             docsDirty_ = true;
             alive_.push_back(1);
             zeroNorm_.push_back(isZeroNorm(r.embedding) ? 1 : 0);
         }
         ranksDirty_ = true;
         return {};
+    }
+    // indices into `records`, one per distinct chunk_id: in the order of the first occurrences, each naming the last one
+    static std::vector<size_t> uniqueInBatch(const std::vector<VectorRecord>& records) {
+        std::vector<size_t> unique;
+        std::unordered_map<std::string, size_t> pos;
+        for (size_t i = 0; i < records.size(); ++i) {
+            auto it = pos.find(records[i].chunk_id);
+            if (it == pos.end()) { pos.emplace(records[i].chunk_id, unique.size()); unique.push_back(i); }
+            else unique[it->second] = i;
+        }
+        return unique;
     }
     Result<void> deleteVector(const std::string& chunkId) {
         auto it = byId_.find(chunkId);
@@ -369,7 +379,7 @@ private:
         return n < 1e-10;
     }
     void kill(size_t row) {
-        if (alive_[row]) { alive_[row] = 0; ++dead_; ranksDirty_ = true; }
+        if (alive_[row]) { alive_[row] = 0; ++dead_; ranksDirty_ = true; ++mirrorGen_; }
     }
     Result<void> upload(size_t first) {
         const size_t n = records_.size() - first;
@@ -401,10 +411,11 @@ private:
         if (dead_ > 1024 && dead_ * 4 > records_.size()) { // compact: drop the tombstones, re-upload
             std::vector<VectorRecord> keep;
             std::vector<uint8_t> zn;
+            std::vector<uint64_t> sn;
             keep.reserve(records_.size() - dead_);
             for (size_t r = 0; r < records_.size(); ++r)
-                if (alive_[r]) { keep.push_back(std::move(records_[r])); zn.push_back(zeroNorm_[r]); }
-            records_.swap(keep); zeroNorm_.swap(zn);
+                if (alive_[r]) { keep.push_back(std::move(records_[r])); zn.push_back(zeroNorm_[r]); sn.push_back(serial_[r]); }
+            records_.swap(keep); zeroNorm_.swap(zn); serial_.swap(sn);
             alive_.assign(records_.size(), 1);
             dead_ = 0;
             byId_.clear(); byDoc_.clear();
@@ -416,9 +427,10 @@ private:
             deviceRows_ = 0;
             docsDirty_ = true;
             ranksDirty_ = true;
+            ++mirrorGen_;   // (row numbers changed, and corpus_clear released the device's PQ tables)
         }
         const bool appended = records_.size() > deviceRows_;
-        if (appended) if (auto u = upload(deviceRows_); !u) return u.error();
+        if (appended) { if (auto u = upload(deviceRows_); !u) return u.error(); ++mirrorGen_; }
         if ((ranksDirty_ || appended) && !records_.empty() && !idOrdered_) {
             // secondary sort key = chunk_id string order (:4218-4223); tombstones keep a rank too
             const size_t n = records_.size();
@@ -532,7 +544,10 @@ public:
     // on the device.  The host keeps simeon (training, encoding, the per-query table).  After every (re)build of its
     // SimeonPqIndexState for this dimension it hands over the codes and, per indexed row, the chunk id (rowids[i] resolved):
     // the tie-break keys (stableStringKey, :141-148, :3337) and the index -> mirror-row table are derived here.  Rows the
-    // mirror does not (or no longer) hold are skipped by the search, as :4010-4012 does.
+    // mirror does not (or no longer) hold are skipped by the search, as :4010-4012 does: the index names ROWIDS, so a row
+    // deleted OR REPLACED after setPqIndex (a replacement takes a new rowid, :1155-1167) is lost to the index until the host
+    // hands over its next build.  The index -> mirror-row table is derived again whenever the mirror changed (a tombstone, an
+    // append, a compaction: mirrorGen_), never by comparing row counts — a compaction can restore the count.
     static uint64_t stableStringKey(const std::string& s) { // FNV-1a 64 (:141-148)
         uint64_t h = 1469598103934665603ULL;
         for (const unsigned char b : s) { h ^= b; h *= 1099511628211ULL; }
@@ -544,18 +559,30 @@ public:
         const size_t n = chunkIdOfIndex.size();
         if (m == 0 || codes.size() != n * m) return Error{ErrorCode::InvalidArgument, "codes must hold m bytes per indexed row"};
         if (auto sy = syncMirror(); !sy) return sy.error();   // (may compact: row numbers are final after it)
+        pqChunkIds_ = chunkIdOfIndex; pqCodes_ = codes; pqM_ = m;
+        pqSerials_.assign(n, 0);                               // the row each index entry names NOW (0: none)
+        for (size_t i = 0; i < n; ++i)
+            if (const auto it = byId_.find(chunkIdOfIndex[i]); it != byId_.end()) pqSerials_[i] = serial_[it->second];
+        return derivePqRows();
+    }
+private:
+    // index -> mirror row for the mirror as it is now, handed to the device with the codes and the tie keys
+    Result<void> derivePqRows() {
+        const size_t n = pqChunkIds_.size();
         std::vector<uint64_t> keys(n);
         std::vector<uint32_t> rowOf(n);
         for (size_t i = 0; i < n; ++i) {
-            keys[i] = stableStringKey(chunkIdOfIndex[i]);
-            const auto it = byId_.find(chunkIdOfIndex[i]);
-            rowOf[i] = it == byId_.end() ? 0xffffffffu : static_cast<uint32_t>(it->second);
+            keys[i] = stableStringKey(pqChunkIds_[i]);
+            const auto it = byId_.find(pqChunkIds_[i]);
+            const bool same = it != byId_.end() && pqSerials_[i] != 0 && serial_[it->second] == pqSerials_[i];
+            rowOf[i] = same ? static_cast<uint32_t>(it->second) : 0xffffffffu;
         }
-        pqChunkIds_ = chunkIdOfIndex; pqCodes_ = codes; pqM_ = m; pqRows_ = records_.size();
-        const yams_status_t st = vt_->pq_index_set(vt_->self, corpus_, codes.data(), n, static_cast<uint32_t>(m), keys.data(), rowOf.data());
+        const yams_status_t st = vt_->pq_index_set(vt_->self, corpus_, pqCodes_.data(), n, static_cast<uint32_t>(pqM_), keys.data(), rowOf.data());
         if (st != YAMS_OK) return Error{accel::mapStatus(st), "pq_index_set failed"};
+        pqGen_ = mirrorGen_;
         return {};
     }
+public:
     // queries: RAW query embeddings; luts[q]: m x 256 floats, simeon::PQInnerProductQuery's table for the NORMALISED query
     // (:3895-3901); candidateIndices (nullable): ascending indices into the PQ index (:3910-3937); sumFlags: YAMS_PQ_SUM_*.
     Result<std::vector<std::vector<VectorRecord>>>
@@ -571,8 +598,8 @@ public:
                 return Error{ErrorCode::InvalidArgument, "query / table size mismatch"};
         if (k > YAMS_SCAN_MAX_K) return Error{ErrorCode::NotSupported, "k exceeds YAMS_SCAN_MAX_K for the product-quantised engine"};
         if (auto sy = syncMirror(); !sy) return sy.error();
-        if (records_.size() != pqRows_ && !pqChunkIds_.empty()) { // the mirror was compacted or grew: the row table is re-derived
-            if (auto r = setPqIndex(pqCodes_, pqM_, pqChunkIds_); !r) return r.error();
+        if (pqGen_ != mirrorGen_ && !pqChunkIds_.empty()) { // the mirror changed since the row table was derived
+            if (auto r = derivePqRows(); !r) return r.error();
         }
         std::vector<float> fq(queries.size() * dim_), fl(queries.size() * pqM_ * 256);
         for (size_t i = 0; i < queries.size(); ++i) {
@@ -606,7 +633,8 @@ public:
     }
 
 private:
-    std::vector<std::string> pqChunkIds_; std::vector<uint8_t> pqCodes_; size_t pqM_ = 0, pqRows_ = 0;
+    std::vector<std::string> pqChunkIds_; std::vector<uint8_t> pqCodes_; std::vector<uint64_t> pqSerials_; size_t pqM_ = 0;
+    uint64_t pqGen_ = 0;          // mirrorGen_ when the device's index -> row table was derived
 
     // k above what one device call returns (YAMS_SCAN_MAX_K): the reference takes any k
     // (sqlite_vec_backend.cpp:4299-4303 keeps a heap of k), callers that over-fetch for fusion or re-ranking
@@ -680,6 +708,9 @@ private:
     bool initialized_ = false, ranksDirty_ = false;
     std::vector<VectorRecord> records_;
     std::vector<uint8_t> alive_, zeroNorm_;
+    std::vector<uint64_t> serial_;   // per row: what a rowid is to the reference — never reused, a replacement gets a new one
+    uint64_t nextSerial_ = 1;
+    uint64_t mirrorGen_ = 1;         // bumped by every tombstone, append and compaction of the device mirror
     size_t dead_ = 0, deviceRows_ = 0;
     std::unordered_map<std::string, size_t> byId_;
     std::unordered_map<std::string, std::vector<uint32_t>> byDoc_; // document_hash -> rows (incl. tombstones)
@@ -706,10 +737,11 @@ public:
 
     Result<void> insertVectorsBatch(const std::vector<VectorRecord>& records) {
         std::map<size_t, std::vector<VectorRecord>> byDim;
-        for (const auto& r : records) {
+        for (const auto& r : records)
             if (r.embedding.empty()) return Error{ErrorCode::InvalidArgument, "empty embedding"};
-            byDim[r.embedding.size()].push_back(r);
-        }
+        // a chunk_id repeated in the batch is ONE row, whatever the sizes of its occurrences: the reference de-duplicates the
+        // whole batch first (:1114-1130, first position, last content), so the last occurrence decides the dimension too
+        for (size_t i : AccelVectorIndex::uniqueInBatch(records)) byDim[records[i].embedding.size()].push_back(records[i]);
         for (auto& [dim, recs] : byDim) {
             // a chunk_id lives in one dimension only: re-inserting it with another size moves it
             for (const auto& r : recs) {

@@ -950,8 +950,10 @@ typedef struct yams_vector_scan_v1 {
      * pq_index_set: the host's SimeonPqIndexState (:48-62) for this corpus, all HOST arrays: codes [n_codes][m],
      * tie_keys [n_codes] (tie_break_keys = stableStringKey(chunk_id)), row_of_index [n_codes] (nullable = identity: which
      * mirror row code i belongs to — rowids[i] mapped to the mirror's ordinal).  Replaces a previous index; n_codes == 0
-     * drops it.  corpus_clear / corpus_append do NOT touch it: the host sets it again after it re-encodes (a PQ index that
-     * names rows the mirror has lost skips them, :4010-4012).  Corpora dealt to several devices: YAMS_ERR_UNSUPPORTED. */
+     * drops it.  corpus_append does NOT touch it (a PQ index that names rows the mirror has lost skips them, :4010-4012).
+     * corpus_clear RELEASES it with the other per-row tables (documents, entity attributes): its row_of_index names rows
+     * that are gone, and rows appended afterwards are different rows — search_pq on a cleared corpus returns nothing until
+     * pq_index_set is called again.  Corpora dealt to several devices: YAMS_ERR_UNSUPPORTED. */
     yams_status_t (*pq_index_set)(void* self, uint64_t corpus_id, const uint8_t* codes, uint64_t n_codes, uint32_t m,
                                   const uint64_t* tie_keys, const uint32_t* row_of_index);
     /* queries: host [n_queries][dim] RAW queries; luts: host [n_queries][m][256] (what simeon::PQInnerProductQuery holds for

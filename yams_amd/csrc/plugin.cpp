@@ -722,6 +722,7 @@ yams_status_t vs_corpus_clear(void*, uint64_t id) {
     if (!c) return YAMS_ERR_NOT_FOUND;
     std::unique_lock<std::shared_mutex> lk(c->mu);
     for (auto& s : c->sh) { s.n_rows = 0; s.has_tie = false; }
+    c->pq.release();        // (its index -> row table names rows that are gone: nothing is searched until pq_index_set comes again)
     c->docs.release();
     c->ents.release();
     c->n_rows = 0; c->has_ranks = false; c->i8_flags = -1; c->i8_decided_rows = 0;
