@@ -367,7 +367,15 @@ YAMS_ACCEL_API yams_status_t yams_scan_topk_host(yams_accel_ctx* ctx,
  * ordinals a shard reports without one) order exact cross-shard ties wrongly.  Callers without a
  * corpus-wide ranking pass in_ranks = NULL (global row ids break ties: right whenever rows were
  * appended in chunk_id order) or use yams_scan_merge_records_device with rank_of_row.
- * For YAMS_SCAN_L2 the similarity_threshold is applied after the merge (:4508-4510). */
+ * For YAMS_SCAN_L2 the similarity_threshold is applied after the merge (:4508-4510): the k nearest first, then the
+ * entries with similarity < threshold are dropped and the survivors keep their order (the freed slots are padding, not
+ * refilled from behind position k).  THIS entry always applies it: YAMS_SCAN_FLAG_DEFER_THRESHOLD in params->flags is
+ * IGNORED here, while yams_scan_merge_records_device honours it (nothing is dropped).  Under cosine the threshold plays
+ * no part in either entry (each shard has applied it), and under L2 the ranks play none (equal distances: row id asc).
+ * Entries equal in every key (one row id in two shards) keep shard order, then list position.  Lists may be shorter
+ * than k or empty (slots at or behind in_counts are never read); n_shards * k <= 8192, else YAMS_ERR_UNSUPPORTED.
+ * out_dist (nullable): in_dist of the entry, or 1 - similarity when in_dist is NULL; unused output slots hold
+ * -inf / -1 / +inf.  tests/_merge_model.py states this contract in numpy; tests/stress_merge.py holds the kernel to it. */
 YAMS_ACCEL_API yams_status_t yams_scan_merge_topk_device(
     yams_accel_ctx* ctx, uint32_t n_shards, uint32_t n_queries, const yams_scan_params_t* params,
     const float* in_scores, const int64_t* in_rows, const uint32_t* in_counts,

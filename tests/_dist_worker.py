@@ -48,15 +48,10 @@ if use_gpu:
                                     g["counts"].data_ptr(), None, None, out["scores"].data_ptr(),
                                     out["rows"].data_ptr(), out["counts"].data_ptr(), None)
 else:
+    from _dist_fallback import python_merge
+
     def merge_fn(g, out):                      # test-only restatement: (similarity desc, row asc)
-        for qi in range(nq):
-            ent = [(-float(g["scores"][s, qi, i]), int(g["rows"][s, qi, i]))
-                   for s in range(world) for i in range(int(g["counts"][s, qi]))]
-            ent.sort()
-            ent = ent[:k]
-            out["counts"][qi] = len(ent)
-            for i, e in enumerate(ent):
-                out["scores"][qi, i] = -e[0]; out["rows"][qi, i] = e[1]
+        python_merge(g, out, world, nq, k)
 pipe.merge_fn = merge_fn
 
 ok = True

@@ -533,12 +533,26 @@ class Accel:
         return ScanResult(scores[:, :k], rows[:, :k], counts, None, diag.as_dict())
 
     def merge_topk_device(self, n_shards, nq, k, threshold, metric, in_scores, in_rows, in_counts,
-                          in_dist, in_ranks, out_scores, out_rows, out_counts, out_dist):
-        prm = ScanParams(k, threshold, metric, 0)
+                          in_dist, in_ranks, out_scores, out_rows, out_counts, out_dist, flags: int = 0):
+        prm = ScanParams(k, threshold, metric, flags)
         self._check(self.L.yams_scan_merge_topk_device(self.ctx, n_shards, nq, C.byref(prm),
                                                        in_scores, in_rows, in_counts, in_dist,
                                                        in_ranks, out_scores, out_rows, out_counts,
                                                        out_dist))
+
+    def record_layout(self, nq: int, k: int, with_dist: bool, with_ranks: bool) -> "_lib.RecordLayout":
+        """yams_scan_record_layout: the offsets of one packed per-shard record (an absent part has offset 2**64 - 1)."""
+        lay = _lib.RecordLayout()
+        self.L.yams_scan_record_layout(nq, k, 1 if with_dist else 0, 1 if with_ranks else 0, C.byref(lay))
+        return lay
+
+    def merge_records_device(self, n_shards, nq, k, threshold, metric, records, record_stride, layout,
+                             rank_of_row, rank_row_base, out_scores, out_rows, out_counts, out_dist, flags: int = 0):
+        """yams_scan_merge_records_device over `n_shards` packed records `record_stride` bytes apart (device pointers)."""
+        prm = ScanParams(k, threshold, metric, flags)
+        self._check(self.L.yams_scan_merge_records_device(self.ctx, n_shards, nq, C.byref(prm), records, record_stride,
+                                                          C.byref(layout) if layout is not None else None, rank_of_row,
+                                                          rank_row_base, out_scores, out_rows, out_counts, out_dist))
 
     def synth_rows(self, seed: int, row0: int, n_rows: int, dim: int, out_ptr: int):
         self._check(self.L.yams_synth_rows_device(self.ctx, seed, row0, n_rows, dim, out_ptr))
