@@ -808,6 +808,12 @@ YAMS_ACCEL_API yams_status_t yams_ingest_device(yams_accel_ctx* ctx, const uint8
  * four device buffers, batch i + 1 uploading while batch i is chunked and hashed.  Device footprint: during the call up
  * to 4 x batch_bytes + ~25 % of tables; AFTER the call the context keeps no buffer above 1.25 GiB (larger ones are
  * freed on return: they belong to the call, not to the context).
+ * How a call is cut into batches (part of the contract: tests/_ingest_model.py restates it and holds the "batches" and
+ * "slots" of device_info's "last_host_ingest" to it): batches hold consecutive blobs in call order; a blob is never split;
+ * inside its batch every blob starts on a 16-byte boundary, so a blob counts with its length rounded up to a multiple of 16
+ * (an empty blob counts 0); a batch always takes at least one blob, however long; a batch closes in front of the first
+ * blob whose rounded length would take its sum past batch_bytes.  Without YAMS_INGEST_BLOB_DIGESTS two slot buffers serve
+ * the batches in turn, with it four; never more buffers than there are batches.
  * Pinned (page-locked) blob memory uploads at link speed, pageable memory through the runtime's
  * staging.  Results go to caller arrays: out_blob_first[n_blobs + 1] (prefix of chunk counts),
  * out_chunk_offset / out_chunk_size [chunk_cap], out_chunk_digest [chunk_cap][32] (nullable),
