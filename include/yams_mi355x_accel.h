@@ -696,6 +696,68 @@ YAMS_ACCEL_API yams_status_t yams_scan_entity_topk_device(
     uint64_t* out_matching, yams_scan_diag_t* diag);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Spherical k-means of document embeddings: the topology engine "kmeans_v1"                    */
+/* ------------------------------------------------------------------------------------------ */
+/* KMeansTopologyEngine::buildArtifacts (src/topology/topology_alternate_engines.cpp:648-675) hands every document-level
+ * embedding to runKMeans (:341-478), a deterministic spherical k-means; these entries are runKMeans over the usable rows
+ * (the shell that filters them is include/yams_accel/topology_kmeans.hpp) and nearestCentroid (:321-336) alone.
+ * The contract, restated from :288-478 and topology_build_utils.h:27-56:
+ *   cosineDistance (:288-305)  dot, na, nb summed in fp64 element by element; 2.0 if na <= 0 || nb <= 0, else
+ *             1 - std::clamp(dot / (sqrt(na) * sqrt(nb)), -1, 1) (std::clamp's comparisons: a NaN passes through).  na and nb
+ *             are computed once per row / centroid by the same chain: the same bits.
+ *   normalized (:307-319)  norm^2 in fp64; inv = float(1.0 / sqrt(norm)); x *= inv in fp32; a zero vector is left as it is.
+ *   meanEmbedding (h:27-56)  an fp32 running sum 0.0f + m0 + m1 + ... over the members in ASCENDING ROW ORDER, /= float(count)
+ *             (the IEEE divide), then normalized.
+ *   k (:367-371)  0 = round(sqrt(n)); then clamped to [2, n].     max_iterations (:413)  0 = 10.
+ *   initialisation (:373-401)  centroid 0 = normalized(row 0); until k centroids exist: over the rows not yet selected,
+ *             minDist[u] = min(minDist[u], d(row u, last centroid)), then the first u with the strictly largest minDist is
+ *             selected and normalized(row u) appended.  (While k <= n a row is always found: k_eff = k.)
+ *   iteration (:414-466)  membership starts at 0; every row moves to its nearest centroid (strict <: the lowest index wins a
+ *             tie, a NaN distance never wins, all NaN = 0) and `changed` records a move; every cluster with members gets
+ *             normalized(mean of its members), one without keeps its centroid; then the repair below; the loop stops after
+ *             the first iteration in which nothing changed.
+ *   empty-cluster repair (:433-462)  empty clusters in cluster order: the first row with the strictly largest distance to
+ *             its OWN, already updated centroid among the clusters holding more than one member moves over; its row,
+ *             normalized, becomes the empty cluster's centroid and the donor's centroid is recomputed from its remaining
+ *             members (order kept); later empty clusters see the updated state; `changed` is set.  Duplicate rows make this
+ *             path run (a duplicate centroid collects no members).
+ * Every finite input is served as the CPU computes it — zero rows, denormal rows (whose normalisation overflows fp32), rows at
+ * +-FLT_MAX / 4 (whose fp32 mean overflows) included; a row with a non-finite element is YAMS_ERR_INVALID_ARG (the
+ * reference's insert path admits finite values only).  Results equal the CPU loop bit for bit: no chain is split.
+ * Limits: 2 <= n < 2^31, dim <= YAMS_CLUSTER_MAX_DIM, k (after the clamp) <= YAMS_CLUSTER_MAX_K: beyond, YAMS_ERR_UNSUPPORTED.
+ * n == 0: YAMS_OK, *out_k = *out_iterations = 0, nothing written.  n == 1 (std::clamp(k, 2, 1) is undefined; the reference's
+ * shell never gets there) or dim == 0: YAMS_ERR_INVALID_ARG.
+ *   rows            device [n][dim] fp32, raw
+ *   out_membership  device [n] uint32: the cluster of every row
+ *   out_centroids   device [k_eff][dim] fp32, nullable; the caller sizes it for the clamped k (n rows is always enough)
+ *   out_k           host, nullable: k_eff          out_iterations  host, nullable: iterations run (the last one included)
+ * Work: N*K*D fp64 multiply-adds per iteration and for the initialisation, which is K dependent steps (no host round trip
+ * between them); per iteration K + 1 words come back (member counts, changed).  The repair path is driven from the host (it
+ * is rare; its distances are computed on the device).  The call synchronises the context's stream before returning. */
+#define YAMS_CLUSTER_MAX_DIM 4096u
+#define YAMS_CLUSTER_MAX_K 65536u
+YAMS_ACCEL_API yams_status_t yams_cluster_kmeans_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, uint32_t k, uint32_t max_iterations,
+    uint32_t* out_membership, float* out_centroids, uint32_t* out_k, uint32_t* out_iterations);
+/* The same over host memory (rows, out_membership, out_centroids are host arrays). */
+YAMS_ACCEL_API yams_status_t yams_cluster_kmeans_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, uint32_t k, uint32_t max_iterations,
+    uint32_t* out_membership, float* out_centroids, uint32_t* out_k, uint32_t* out_iterations);
+/* nearestCentroid (:321-336) of every row over GIVEN centroids (incremental routing): out_assign[u] = the lowest index among
+ * the centroids at the smallest cosineDistance; a centroid whose centroid_empty flag is non-zero is skipped (:326-328: an
+ * empty vector); a NaN distance never wins; a row no centroid wins (all skipped, all NaN, n_centroids == 0) gets 0.
+ *   rows            device [n][dim]            centroids  device [n_centroids][dim], raw (no normalisation; non-finite values
+ *                                                         are served: they give NaN distances)
+ *   centroid_empty  device [n_centroids] uint8, nullable (= none)
+ *   out_assign      device [n] uint32          out_distance  device [n] fp64, nullable: the winner's distance (DBL_MAX, the
+ *                                                         loop's initial bestDist, when no centroid won)
+ * n == 0: YAMS_OK.  dim == 0: YAMS_ERR_INVALID_ARG.  Non-finite ROWS: YAMS_ERR_INVALID_ARG.  The limits above.
+ * The call synchronises the context's stream before returning. */
+YAMS_ACCEL_API yams_status_t yams_cluster_assign_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_centroids,
+    const uint8_t* centroid_empty, uint32_t* out_assign, double* out_distance);
+
+/* ------------------------------------------------------------------------------------------ */
 /* SHA-256                                                                                      */
 /* ------------------------------------------------------------------------------------------ */
 /* Digest n_msgs byte ranges of one device buffer: message i = data[offsets[i] .. +lengths[i]).
@@ -1026,6 +1088,27 @@ typedef struct yams_vector_entity_scan_v1 {
                                      uint32_t** out_counts, uint64_t* out_matching, yams_scan_diag_t* out_diag);
     void (*free_entity_hits)(void* self, yams_scan_hit_t* hits, uint32_t* counts);
 } yams_vector_entity_scan_v1;
+
+/* The topology build's k-means (yams_cluster_kmeans_device / yams_cluster_assign_device) for a host that holds the
+ * embeddings in its own memory.  A separate interface, version 1, served by yams_plugin_get_interface and NOT listed in
+ * the manifest, for the reason given at vector_doc_scan_v1.  Host memory in, host memory out. */
+#define YAMS_IFACE_TOPOLOGY_CLUSTER_V1 "topology_cluster_v1"
+#define YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION 1u
+typedef struct yams_topology_cluster_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION */
+    void* self;
+    /* runKMeans over rows [n][dim] (every row usable): *out_membership [n] and *out_centroids [*out_k][dim] are allocated
+     * by the plugin (release with free_clusters); out_centroids, out_k, out_iterations are nullable.  Statuses and limits
+     * of yams_cluster_kmeans_device; n == 0 gives null arrays. */
+    yams_status_t (*kmeans)(void* self, const float* rows, uint64_t n, uint32_t dim, uint32_t k, uint32_t max_iterations,
+                            uint32_t** out_membership, float** out_centroids, uint32_t* out_k, uint32_t* out_iterations);
+    /* nearestCentroid of rows [n][dim] over centroids [n_centroids][dim]; centroid_empty [n_centroids] nullable;
+     * *out_assign [n] and *out_distance [n] (nullable: not wanted) are allocated by the plugin (free_assignment). */
+    yams_status_t (*assign)(void* self, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_centroids,
+                            const uint8_t* centroid_empty, uint32_t** out_assign, double** out_distance);
+    void (*free_clusters)(void* self, uint32_t* membership, float* centroids);
+    void (*free_assignment)(void* self, uint32_t* assign, double* distance);
+} yams_topology_cluster_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

@@ -192,6 +192,20 @@ class VectorEntityScanV1(C.Structure):  # vector_entity_scan_v1 (served by get_i
     ]
 
 
+class TopologyClusterV1(C.Structure):  # topology_cluster_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("kmeans", C.CFUNCTYPE(ST, vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u32p), C.POINTER(f32p), u32p, u32p)),
+        ("assign", C.CFUNCTYPE(ST, vp, f32p, C.c_uint64, C.c_uint32, f32p, C.c_uint32, u8p, C.POINTER(u32p),
+                               C.POINTER(C.POINTER(C.c_double)))),
+        ("free_clusters", C.CFUNCTYPE(None, vp, u32p, f32p)),
+        ("free_assignment", C.CFUNCTYPE(None, vp, u32p, C.POINTER(C.c_double))),
+    ]
+
+
+CLUSTER_MAX_DIM, CLUSTER_MAX_K = 4096, 65536     # YAMS_CLUSTER_MAX_DIM / _MAX_K
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -246,6 +260,7 @@ EXPORTS = [
     "yams_accel_debug_fail_alloc_after", "yams_accel_debug_alloc_faults", "yams_accel_debug_alloc_injection_compiled",
     "yams_scan_topk_device", "yams_scan_topk_host", "yams_scan_merge_topk_device", "yams_scan_pq_topk_device",
     "yams_scan_doc_topk_device", "yams_scan_entity_topk_device",
+    "yams_cluster_kmeans_device", "yams_cluster_kmeans_host", "yams_cluster_assign_device",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -332,6 +347,9 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
                                             vp, vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_entity_topk_device.argtypes = [vp, C.POINTER(ScanCorpus), C.POINTER(ScanEntities), vp, C.POINTER(EntityFilter),
                                                C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, C.POINTER(ScanDiag)]
+    L.yams_cluster_kmeans_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u32p, u32p]
+    L.yams_cluster_kmeans_host.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u32p, u32p]
+    L.yams_cluster_assign_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

@@ -482,6 +482,72 @@ class Accel:
         r.matching = matching
         return r
 
+    def _effective_k(self, n: int, k: int) -> int:
+        kk = k if k else int(np.floor(np.sqrt(float(n)) + 0.5))
+        return min(max(kk, 2), n)
+
+    def cluster_kmeans_device(self, rows_ptr: int, n: int, dim: int, k: int = 0, max_iterations: int = 0,
+                              membership_ptr: int | None = None, centroids_ptr: int | None = None):
+        """yams_cluster_kmeans_device over device arrays; returns (k_eff, iterations run)."""
+        ke = C.c_uint32(); it = C.c_uint32()
+        self._check(self.L.yams_cluster_kmeans_device(self.ctx, rows_ptr, n, dim, k, max_iterations, membership_ptr, centroids_ptr,
+                                                      C.byref(ke), C.byref(it)))
+        return ke.value, it.value
+
+    def cluster_kmeans(self, rows: np.ndarray, k: int = 0, max_iterations: int = 0, host_entry: bool = False):
+        """The topology build's spherical k-means (runKMeans of engine kmeans_v1) of host rows [n][dim]: returns
+        (membership [n] uint32, centroids [k_eff][dim] float32, k_eff, iterations run).  host_entry=True goes through
+        yams_cluster_kmeans_host instead of uploading here."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        assert x.ndim == 2
+        n, dim = x.shape
+        if n == 0:
+            ke, it = self.cluster_kmeans_device(None, 0, dim, k, max_iterations)
+            return np.zeros(0, np.uint32), np.zeros((0, dim), np.float32), ke, it
+        kmax = self._effective_k(n, k)
+        if host_entry:
+            mem = np.zeros(n, np.uint32); cent = np.zeros((kmax, dim), np.float32)
+            ke = C.c_uint32(); it = C.c_uint32()
+            self._check(self.L.yams_cluster_kmeans_host(self.ctx, x.ctypes.data, n, dim, k, max_iterations, mem.ctypes.data, cent.ctypes.data,
+                                                        C.byref(ke), C.byref(it)))
+            return mem, cent[:ke.value], ke.value, it.value
+        d_x = self.to_device(x) if x.size else None
+        d_m = self.alloc(n * 4 + 16); d_c = self.alloc(kmax * dim * 4 + 16)
+        try:
+            ke, it = self.cluster_kmeans_device(d_x.ptr if d_x else None, n, dim, k, max_iterations, d_m.ptr, d_c.ptr)
+            mem = d_m.download(np.uint32, n)
+            cent = d_c.download(np.float32, ke * dim).reshape(ke, dim)
+        finally:
+            for b in (d_x, d_m, d_c):
+                if b is not None:
+                    b.free()
+        return mem, cent, ke, it
+
+    def cluster_assign(self, rows: np.ndarray, centroids: np.ndarray, empty: np.ndarray | None = None, with_distance: bool = True):
+        """nearestCentroid of every host row over host centroids (yams_cluster_assign_device): (assign [n] uint32, distance
+        [n] float64 or None).  empty: per-centroid flags of centroids to skip."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        n, dim = x.shape
+        c = np.ascontiguousarray(centroids, dtype=np.float32).reshape(-1, dim) if dim else np.zeros((0, 0), np.float32)
+        nc = c.shape[0]
+        if n == 0:
+            self._check(self.L.yams_cluster_assign_device(self.ctx, None, 0, dim, None, nc, None, None, None))
+            return np.zeros(0, np.uint32), (np.zeros(0, np.float64) if with_distance else None)
+        d_x = self.to_device(x) if x.size else None
+        d_c = self.to_device(c) if c.size else None
+        d_e = self.to_device(np.ascontiguousarray(empty, dtype=np.uint8)) if empty is not None and nc else None
+        d_a = self.alloc(n * 4 + 16); d_d = self.alloc(n * 8 + 16) if with_distance else None
+        try:
+            self._check(self.L.yams_cluster_assign_device(self.ctx, d_x.ptr if d_x else None, n, dim, d_c.ptr if d_c else None, nc,
+                                                          d_e.ptr if d_e else None, d_a.ptr, d_d.ptr if d_d else None))
+            a = d_a.download(np.uint32, n)
+            dist = d_d.download(np.float64, n) if d_d else None
+        finally:
+            for b in (d_x, d_c, d_e, d_a, d_d):
+                if b is not None:
+                    b.free()
+        return a, dist
+
     def scan_pq_topk(self, corpus: ScanCorpus, codes: np.ndarray, luts: np.ndarray, queries: np.ndarray, k: int, threshold: float = -1.0,
                      rerank_factor: int = 2, tie_keys: np.ndarray | None = None, row_of_index: np.ndarray | None = None,
                      candidates: np.ndarray | None = None, sum_lanes: int = 1) -> ScanResult:

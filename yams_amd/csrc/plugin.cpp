@@ -7,8 +7,10 @@
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
 // yams_plugin_get_manifest_json, then yams_plugin_get_interface(id, version, &vtable).
 #include <algorithm>
+#include <algorithm>
 #include <atomic>
 #include <cctype>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -1186,6 +1188,72 @@ void es_free_entity_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::
 yams_vector_entity_scan_v1 g_vector_entity_scan = {YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION, nullptr, GUARDED(es_corpus_set_attributes),
                                                    GUARDED(es_search_entities), GUARDED(es_free_entity_hits)};
 
+// ---- topology_cluster_v1: the topology build's k-means over host memory (yams_cluster_kmeans_host / _assign_device) --------
+yams_status_t tc_kmeans(void*, const float* rows, uint64_t n, uint32_t dim, uint32_t k, uint32_t max_iterations,
+                        uint32_t** out_membership, float** out_centroids, uint32_t* out_k, uint32_t* out_iterations) {
+    NEED_INIT();
+    if (!out_membership) return YAMS_ERR_INVALID_ARG;
+    *out_membership = nullptr;
+    if (out_centroids) *out_centroids = nullptr;
+    if (out_k) *out_k = 0;
+    if (out_iterations) *out_iterations = 0;
+    if (n == 0) return YAMS_OK;
+    if (dim == 0 || !rows || n < 2) return YAMS_ERR_INVALID_ARG;
+    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM) return YAMS_ERR_UNSUPPORTED;
+    // the clamped k bounds the centroid array (:367-371)
+    uint64_t kk = k ? k : static_cast<uint64_t>(std::round(std::sqrt(static_cast<double>(n))));
+    kk = std::min<uint64_t>(std::max<uint64_t>(kk, 2), n);
+    if (kk > YAMS_CLUSTER_MAX_K) return YAMS_ERR_UNSUPPORTED;
+    auto* mem = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n) * 4));
+    auto* cent = out_centroids ? static_cast<float*>(std::malloc(static_cast<size_t>(kk) * dim * 4)) : nullptr;
+    if (!mem || (out_centroids && !cent)) { std::free(mem); std::free(cent); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    const yams_status_t st = yams_cluster_kmeans_host(w.v, rows, n, dim, k, max_iterations, mem, cent, out_k, out_iterations);
+    if (st != YAMS_OK) { std::free(mem); std::free(cent); return st; }
+    *out_membership = mem;
+    if (out_centroids) *out_centroids = cent;
+    return YAMS_OK;
+}
+
+yams_status_t tc_assign(void*, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_centroids,
+                        const uint8_t* centroid_empty, uint32_t** out_assign, double** out_distance) {
+    NEED_INIT();
+    if (!out_assign) return YAMS_ERR_INVALID_ARG;
+    *out_assign = nullptr;
+    if (out_distance) *out_distance = nullptr;
+    if (n == 0) return YAMS_OK;
+    if (dim == 0 || !rows || (n_centroids && !centroids)) return YAMS_ERR_INVALID_ARG;
+    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM || n_centroids > YAMS_CLUSTER_MAX_K) return YAMS_ERR_UNSUPPORTED;
+    auto* asg = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n) * 4));
+    auto* dist = out_distance ? static_cast<double*>(std::malloc(static_cast<size_t>(n) * 8)) : nullptr;
+    if (!asg || (out_distance && !dist)) { std::free(asg); std::free(dist); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    auto done = [&](yams_status_t st) { if (st != YAMS_OK) { std::free(asg); std::free(dist); } else { *out_assign = asg; if (out_distance) *out_distance = dist; } return st; };
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    yams_accel_ctx* x = w.v;
+    const size_t rb = static_cast<size_t>(n) * dim * 4, cb = static_cast<size_t>(n_centroids) * dim * 4;
+    float* d_rows; float* d_cent; uint8_t* d_empty = nullptr; uint32_t* d_asg; double* d_dist = nullptr;
+    yams_status_t st;
+    if ((st = yams_accel::ws_get(x, "plugin_tc_rows", rb, (void**)&d_rows)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_tc_centroids", cb + 16, (void**)&d_cent)) != YAMS_OK) return done(st);
+    if ((st = yams_accel::ws_get(x, "plugin_tc_assign", static_cast<size_t>(n) * 4, (void**)&d_asg)) != YAMS_OK) return done(st);
+    if (out_distance && (st = yams_accel::ws_get(x, "plugin_tc_distance", static_cast<size_t>(n) * 8, (void**)&d_dist)) != YAMS_OK) return done(st);
+    if (centroid_empty && n_centroids) {
+        if ((st = yams_accel::ws_get(x, "plugin_tc_empty", n_centroids, (void**)&d_empty)) != YAMS_OK) return done(st);
+        if (yams_accel_upload(x, d_empty, centroid_empty, n_centroids) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
+    }
+    if (yams_accel_upload(x, d_rows, rows, rb) != YAMS_OK || (cb && yams_accel_upload(x, d_cent, centroids, cb) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
+    if ((st = yams_cluster_assign_device(x, d_rows, n, dim, d_cent, n_centroids, d_empty, d_asg, d_dist)) != YAMS_OK) return done(st);
+    if (yams_accel_download(x, asg, d_asg, static_cast<size_t>(n) * 4) != YAMS_OK ||
+        (dist && yams_accel_download(x, dist, d_dist, static_cast<size_t>(n) * 8) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
+    return done(YAMS_OK);
+}
+
+void tc_free_clusters(void*, uint32_t* membership, float* centroids) { std::free(membership); std::free(centroids); }
+void tc_free_assignment(void*, uint32_t* assign, double* distance) { std::free(assign); std::free(distance); }
+
+yams_topology_cluster_v1 g_topology_cluster = {YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION, nullptr, GUARDED(tc_kmeans), GUARDED(tc_assign),
+                                               GUARDED(tc_free_clusters), GUARDED(tc_free_assignment)};
+
 // ---- content_hash_v1 --------------------------------------------------------------------------
 // Every call leases one of the plugin's work contexts (own stream, own workspace), so hashing, chunking
 // and searches of different host threads overlap on the device instead of queueing on one mutex.
@@ -1690,6 +1758,10 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
     if (std::strcmp(iface_id, YAMS_IFACE_VECTOR_ENTITY_SCAN_V1) == 0) { // (not in the manifest: see the header)
         if (version < 1 || version > YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
         *out_iface = &g_vector_entity_scan; return YAMS_PLUGIN_OK;
+    }
+    if (std::strcmp(iface_id, YAMS_IFACE_TOPOLOGY_CLUSTER_V1) == 0) { // (not in the manifest: see the header)
+        if (version < 1 || version > YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
+        *out_iface = &g_topology_cluster; return YAMS_PLUGIN_OK;
     }
     if (std::strcmp(iface_id, YAMS_IFACE_CONTENT_HASH_V1) == 0) {
         if (version < 1 || version > YAMS_IFACE_CONTENT_HASH_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
