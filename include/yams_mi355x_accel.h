@@ -279,7 +279,21 @@ typedef struct yams_scan_diag_s {
     uint64_t rescored_rows;               /* rows re-scored in fp64                              */
     uint32_t widened_queries;             /* queries whose candidate set had to be widened       */
     uint32_t exact_fallback_queries;      /* queries that took the full fp64 scan                */
-    uint32_t path;                        /* 0 = mfma filter + fp64 re-score, 1 = full fp64 scan */
+    uint32_t path;                        /* 0 = mfma filter + fp64 re-score, 1 = full fp64 scan: every allowed row is
+                                             scored in fp64, no filter.  Which one yams_scan_topk_* takes is a contract
+                                             (tests/_score_edges.py restates it), the result is the same bit for bit:
+                                             1 from the FUSED ONE-LAUNCH scan (its launch is the timed region
+                                             "small_scan" of yams_accel_last_kernel_ms), taken exactly when
+                                               1 <= n_rows <= 16384 and n_queries <= 16;
+                                               dim % 32 == 0, dim <= 1024, `rows` 16-byte aligned;
+                                               k <= 256 and ceil(n_rows / 256) * min(k, 256) <= 1024;
+                                               none of FORCE_EXACT, F32_FILTER, SPLIT_FILTER, WIDE_TILE, NO_I8_FILTER,
+                                               RESIDENT_QUERIES; under YAMS_SCAN_L2 no fp32-accumulate flag
+                                               (YAMS_SCAN_FLAG_L2_ACC_* other than F64);
+                                             1 from the exhaustive multi-launch pipeline otherwise when FORCE_EXACT is
+                                             set, n_rows < 4096, `rows` is not 16-byte aligned or dim % 4 != 0, an
+                                             allow-mask admits fewer than 16384 rows, or (L2) a query norm lies outside
+                                             [1e-15, 1e15); 0 in every other case.                                    */
     uint32_t escalated_queries;           /* queries re-filtered with the split (3-pass) filter  */
     uint32_t filter_tier;                 /* first filter tier of the call: 0 none (fp64 scan),
                                              1 int8, 2 bf16, 3 split bf16, 4 f32                  */

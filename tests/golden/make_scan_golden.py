@@ -33,6 +33,45 @@ SKIP_QUERIES = [SKIP_ROWS[0], SKIP_ROWS[5], SKIP_ROWS[9], f32bits(1, 1, 1, 1, 1,
 BAD_QUERIES = [f32bits(0, 0, 0, 0, 0, 0, 0, 0), f32bits(np.nan, 0, 0, 0, 0, 0, 0, 0), f32bits(np.inf, 0, 0, 0, 0, 0, 0, 0),
                f32bits(9e-6, 0, 0, 0, 0, 0, 0, 0), f32bits(1.1e-5, 0, 0, 0, 0, 0, 0, 0)]
 
+
+
+# ---- signed zeros: -0.0f == +0.0f under the reference's float compares (:4218-4223, :4296-4298, :100-120), so the two zeros
+# are ONE score and the chunk id decides.  q = e0 + 1e-30 e1; a row with x0 = 0 and x1 = -1e-30 has a dot of -1e-60, the fp64
+# quotient becomes -0.0f in the cast (:4276); x1 = +1e-30 or 0 gives +0.0f.  Two positives, six rows of the zero plateau
+# (distinct x2: distinct norms, one score), four negatives; the chunk ids put -0.0 rows 7 and 5 ahead of +0.0 rows 4 and 6.
+def _sz_row(dim, x0, x1, x2):
+    return f32bits(x0, x1, x2, *([0.0] * (dim - 3)))
+
+
+def _sz_rows(dim):
+    return [_sz_row(dim, 1, 0, 0), _sz_row(dim, 1, 0, 2),
+            _sz_row(dim, 0, -1e-30, 1.0), _sz_row(dim, 0, 1e-30, 1.5), _sz_row(dim, 0, 0, 2.0),
+            _sz_row(dim, 0, -1e-30, 2.5), _sz_row(dim, 0, 1e-30, 3.0), _sz_row(dim, 0, -1e-30, 3.5),
+            _sz_row(dim, -1, 0, 3), _sz_row(dim, -1, 0, 2), _sz_row(dim, -1, 0, 1), _sz_row(dim, -1, 0, 0)]
+
+
+SZ_RANKS = [5, 3, 9, 1, 7, 2, 11, 0, 4, 6, 8, 10]
+SZ_IDS = ["z%06d" % r for r in SZ_RANKS]            # (explicit ids: the chunk-id order IS the tie rank, shuffled against the row order)
+DENORM_MIN = float(np.float32(1e-45))               # the smallest positive denormal: drops the whole plateau
+
+
+def _sz_case(name, dim, k, threshold, path="fast"):
+    c = {"name": name, "path": path, "k": k, "threshold": threshold, "chunk_ids": SZ_IDS,
+         "corpus": {"kind": "bits", "rows": _sz_rows(dim)}, "queries": {"kind": "bits", "rows": [_sz_row(dim, 1, 1e-30, 0)]}}
+    if path == "record":
+        c["allow_every"] = 1
+    return c
+
+
+SIGNED_ZERO_CASES = [
+    *[_sz_case(f"signed_zero_plateau_x32_k{k}", 32, k, -1.0) for k in (4, 5, 8, 12)],   # dim 32: the fused one-launch path
+    _sz_case("signed_zero_plateau_x32_threshold_pos_zero", 32, 8, 0.0),
+    _sz_case("signed_zero_plateau_x32_threshold_neg_zero", 32, 8, -0.0),
+    _sz_case("signed_zero_plateau_x32_threshold_denorm_min", 32, 8, DENORM_MIN),
+    _sz_case("signed_zero_plateau_x32_record_path_k5", 32, 5, -1.0, path="record"),
+    _sz_case("signed_zero_plateau_x8_k5", 8, 5, -1.0),                                   # dim 8: the general path
+]
+
 CASES = [
     # BASELINE config 1 on the reference's own embedding recipe
     {"name": "config1_mt19937_10k_x384_top10", "path": "fast", "k": 10, "threshold": -1.0,
@@ -78,6 +117,7 @@ CASES = [
      "queries": {"kind": "philox", "seed": 35, "row0": 1 << 40, "n": 5, "dim": 256}},
     {"name": "record_path_philox_4000_x256_top50", "path": "record", "k": 50, "threshold": -1.0, "allow_every": 2,
      "corpus": {"kind": "philox", "seed": 31, "n": 4000, "dim": 256}, "queries": {"kind": "philox", "seed": 31, "row0": 1 << 40, "n": 4, "dim": 256}},
+    *SIGNED_ZERO_CASES,
 ]
 
 
@@ -114,13 +154,18 @@ def main():
         c = dict(case)
         c["expected"] = expected
         out_cases.append(c)
-    spans = open(os.path.join(_oracle.ORACLE_DIR, "_ref", "scan_ref_spans.txt")).read().split("\n")
+    spans = [s for s in open(os.path.join(_oracle.ORACLE_DIR, "_ref", "scan_ref_spans.txt")).read().split("\n") if s]
+    path = os.path.join(HERE, "scan.json")
+    if os.path.exists(path):        # the spans this file's loop was cut from stay as recorded while the library still holds them
+        with open(path) as f:       # (the library has since grown the vec0 spans of scan_l2.json: not this file's business)
+            old = json.load(f).get("reference_spans", [])
+        if old and set(old) <= set(spans):
+            spans = old
     doc = {"generator": "tests/golden/make_scan_golden.py",
            "what": "outputs of the reference's own bruteForceSearchUnlocked (compiled from /root/reference by oracle/Makefile: "
                    "_ref/libyams_scan_ref.so) on regenerable inputs; rows = ordinals in result order, score_bits = the fp32 bits of "
                    "relevance_score",
-           "reference_spans": [s for s in spans if s], "cases": out_cases}
-    path = os.path.join(HERE, "scan.json")
+           "reference_spans": spans, "cases": out_cases}
     with open(path, "w") as f:
         json.dump(doc, f, separators=(",", ":"))
     print("wrote", path, os.path.getsize(path), "bytes,", len(out_cases), "cases,", sum(len(c["expected"]) for c in out_cases), "queries")

@@ -1875,7 +1875,8 @@ def test_hip_scan_reproduces_the_reference_compiled_golden_vectors(acc, oracle, 
             assert r.rows[j, :cnt].tolist() == e["rows"], (case["name"], qi, r.diag)
             assert [int(x) for x in r.scores[j, :cnt].view(np.uint32)] == e["score_bits"], (case["name"], qi)
         n_cases += 1
-    assert n_cases >= (6 if shadow == "both" else 15)
+    # (+9: the signed-zero plateau cases, dim 32 -> the fused path, dim 8 -> the general one; "both" needs dim >= 256: none of them)
+    assert n_cases >= (6 if shadow == "both" else 24)
 
 
 # ---- the reference's own vec0SearchUnlocked, compiled, as golden vectors (round 6) ---------------------------------------------

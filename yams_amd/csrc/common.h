@@ -37,6 +37,29 @@ __host__ __device__ inline float ord2f(uint32_t k) {
 __host__ __device__ inline uint64_t pack_key(float score, uint32_t idx) {
     return (static_cast<uint64_t>(f2ord(score)) << 32) | static_cast<uint64_t>(0xffffffffu - idx);
 }
+// The reference orders cosine results with a FLOAT compare (sqlite_vec_backend.cpp:4218-4223, :4296-4298, :100-120):
+// -0.0f == +0.0f there, the two zeros are ONE score and the tie rank decides between them — while f2ord puts every +0.0f
+// above every -0.0f.  A cosine key therefore carries the canonical zero; the score a caller is GIVEN keeps its own sign
+// bit (the reference returns -0.0f where the fp64 quotient underflows from below), which a selection either keeps
+// beside the key or recovers by scoring the winner again (exact_cosine_again).  L2 keys (-distance: always -0.0f at
+// distance zero) have one zero only.
+__host__ __device__ inline uint64_t pack_cosine_key(float sim, uint32_t idx) {
+    return pack_key(sim == 0.0f ? 0.0f : sim, idx);
+}
+#if defined(__HIPCC__)
+// The fp64 cosine of one row as the scan kernels compute it (:4253-4276: one sequential chain per sum, element by
+// element), for a winner whose key says "zero": only the sign of the zero is news, the row is known to be valid.
+__device__ inline float exact_cosine_again(const float* x, const float* q, uint32_t dim, double qn) {
+    double nsq = 0.0, dot = 0.0;
+    for (uint32_t i = 0; i < dim; ++i) {
+        const double sv = static_cast<double>(x[i]);
+        nsq = fma(sv, sv, nsq);
+        dot = fma(sv, static_cast<double>(q[i]), dot);
+    }
+    const double denom = sqrt(nsq) * qn;
+    return static_cast<float>(denom > 0.0 ? dot / denom : 0.0);
+}
+#endif
 __host__ __device__ inline uint32_t key_idx(uint64_t k) {
     return 0xffffffffu - static_cast<uint32_t>(k);
 }

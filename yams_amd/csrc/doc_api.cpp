@@ -24,7 +24,8 @@ hipError_t launch_doc_sel_keys(hipStream_t st, const unsigned long long* doc_key
                                uint32_t n_slots, unsigned long long* sel);
 hipError_t launch_doc_rank_inverse(hipStream_t st, const uint32_t* doc_rank, uint32_t n_docs, uint32_t* inv, uint32_t* bad);
 hipError_t launch_doc_emit(hipStream_t st, const unsigned long long* res, uint64_t res_stride, const unsigned long long* doc_key,
-                           uint32_t n_docs, const uint32_t* rank_inv, const uint32_t* rank_row, int64_t row_base, uint32_t q0,
+                           uint32_t n_docs, const float* rows, uint32_t dim, const float* queries, const double* qnorm,
+                           const uint32_t* rank_inv, const uint32_t* rank_row, int64_t row_base, uint32_t q0,
                            uint32_t n_slots, uint32_t k, float* out_scores, int64_t* out_rows, uint32_t* out_docs,
                            uint32_t* out_counts);
 }
@@ -136,8 +137,8 @@ extern "C" yams_status_t yams_scan_doc_topk_device(yams_accel_ctx* ctx, const ya
                                          &res_stride));
             tr.end();
         }
-        YA_HIP(ctx, launch_doc_emit(st, reinterpret_cast<const unsigned long long*>(res), res_stride, d_key, n_docs, d_rank_inv,
-                                    rank_row, corpus->row_base, q0, ns, k, out_scores, out_rows, out_docs, out_counts));
+        YA_HIP(ctx, launch_doc_emit(st, reinterpret_cast<const unsigned long long*>(res), res_stride, d_key, n_docs, corpus->rows,
+                                    dim, queries, d_qnorm, d_rank_inv, rank_row, corpus->row_base, q0, ns, k, out_scores, out_rows, out_docs, out_counts));
     }
     if (out_matching) YA_HIP(ctx, hipMemcpyAsync(out_matching, d_match, static_cast<size_t>(nq) * 8, hipMemcpyDeviceToDevice, st));
 

@@ -10,7 +10,7 @@
 // Two launches per slice of queries:
 //   doc_score_kernel   every allowed row is read from HBM once per group of QG queries (row chunks staged through LDS with
 //                      16-byte loads), scored in fp64 in the reference's element order, counted, and its key
-//                      pack_key(sim, tie rank) reduced per document: a segmented max over the runs of equal documents
+//                      pack_cosine_key(sim, tie rank) reduced per document: a segmented max over the runs of equal documents
 //                      inside a wave, then one atomicMax per run into doc_key[slot][doc]
 //   doc_sel_keys_kernel + topk_multilevel + doc_emit_kernel
 //                      the best k documents by (score desc, doc_rank asc) and their rows
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kDocThreads) void doc_score_kernel(
             const double sd = denom > 0.0 ? dot[j] / denom : 0.0;
             if (isfinite(sd)) {
                 const float sim = static_cast<float>(sd);
-                if (!(sim < threshold)) key[j] = pack_key(sim, kidx);
+                if (!(sim < threshold)) key[j] = pack_cosine_key(sim, kidx);   // (one zero: common.h)
             }
         }
     }
@@ -189,8 +189,12 @@ __global__ __launch_bounds__(256) void doc_rank_check_kernel(const uint32_t* doc
 }
 
 // The k winners of every slot: score, row (row_base + ordinal), document ordinal, count; unused slots -inf / -1 / NO_DOC.
+// A key holds the canonical zero (-0.0f and +0.0f are one score to the reference's compares, :100-120): a winner whose
+// similarity is a zero is scored again with the same chains for the sign of ITS zero.
 __global__ __launch_bounds__(256) void doc_emit_kernel(const unsigned long long* res, uint64_t res_stride,
                                                        const unsigned long long* doc_key, uint32_t n_docs,
+                                                       const float* __restrict__ rows, uint32_t dim,
+                                                       const float* __restrict__ queries, const double* __restrict__ qnorm,
                                                        const uint32_t* rank_inv, const uint32_t* rank_row, int64_t row_base,
                                                        uint32_t q0, uint32_t k, float* out_scores, int64_t* out_rows,
                                                        uint32_t* out_docs, uint32_t* out_counts) {
@@ -208,8 +212,11 @@ __global__ __launch_bounds__(256) void doc_emit_kernel(const unsigned long long*
         if (d < n_docs) {
             const unsigned long long dk = doc_key[static_cast<uint64_t>(slot) * n_docs + d];
             const uint32_t kidx = key_idx(dk);
-            out_scores[o] = key_score(dk);
-            out_rows[o] = row_base + static_cast<int64_t>(rank_row ? rank_row[kidx] : kidx);
+            const uint32_t row = rank_row ? rank_row[kidx] : kidx;
+            float sim = key_score(dk);
+            if (sim == 0.0f) sim = exact_cosine_again(rows + static_cast<uint64_t>(row) * dim, queries + static_cast<uint64_t>(q) * dim, dim, qnorm[q]);
+            out_scores[o] = sim;
+            out_rows[o] = row_base + static_cast<int64_t>(row);
             if (out_docs) out_docs[o] = d;
             atomicAdd(&s_n, 1u);
         } else {
@@ -261,12 +268,13 @@ hipError_t launch_doc_rank_inverse(hipStream_t st, const uint32_t* doc_rank, uin
 }
 
 hipError_t launch_doc_emit(hipStream_t st, const unsigned long long* res, uint64_t res_stride, const unsigned long long* doc_key,
-                           uint32_t n_docs, const uint32_t* rank_inv, const uint32_t* rank_row, int64_t row_base, uint32_t q0,
+                           uint32_t n_docs, const float* rows, uint32_t dim, const float* queries, const double* qnorm,
+                           const uint32_t* rank_inv, const uint32_t* rank_row, int64_t row_base, uint32_t q0,
                            uint32_t n_slots, uint32_t k, float* out_scores, int64_t* out_rows, uint32_t* out_docs,
                            uint32_t* out_counts) {
     if (n_slots == 0) return hipSuccess;
-    hipLaunchKernelGGL(doc_emit_kernel, dim3(n_slots), dim3(256), 0, st, res, res_stride, doc_key, n_docs, rank_inv, rank_row,
-                       row_base, q0, k, out_scores, out_rows, out_docs, out_counts);
+    hipLaunchKernelGGL(doc_emit_kernel, dim3(n_slots), dim3(256), 0, st, res, res_stride, doc_key, n_docs, rows, dim, queries,
+                       qnorm, rank_inv, rank_row, row_base, q0, k, out_scores, out_rows, out_docs, out_counts);
     return hipGetLastError();
 }
 

@@ -789,7 +789,7 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
     if (rs > RS_MAX) rs = RS_MAX;
     uint64_t* skey = reinterpret_cast<uint64_t*>(smem);              // [rs]
     uint32_t* sidx = reinterpret_cast<uint32_t*>(skey + rs);         // [rs] candidate slot
-    float* saux = reinterpret_cast<float*>(sidx + rs);               // [rs] cosine (L2 mode)
+    float* saux = reinterpret_cast<float*>(sidx + rs);               // [rs] the similarity returned (its own zero; L2: the cosine)
     float* sq = saux + rs;                                           // [dim]
     float* sstage = sq + ((a.dim + 3u) & ~3u);                       // [waves][64 rows][RS_STAGE_STRIDE] (staged walk)
 
@@ -960,7 +960,8 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
             const double cs = (na == 0.0 || nb == 0.0) ? 0.0 : dot / (na * nb);
             const float sim = static_cast<float>(cs);
             if (sim < a.threshold || sim != sim) continue;
-            skey[c] = pack_key(sim, rank);
+            saux[c] = sim;                                          // (the key holds the canonical zero: common.h)
+            skey[c] = pack_cosine_key(sim, rank);
             sidx[c] = c;
         } else if (METRIC == YAMS_SCAN_COSINE) {
             // all elements finite <=> nsq finite (fp64 cannot overflow on fp32 squares)
@@ -980,7 +981,8 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
             }
 #endif
             if (sim < a.threshold) continue;                        // :4277-4279
-            skey[c] = pack_key(sim, rank);
+            saux[c] = sim;                                          // (the key holds the canonical zero: common.h)
+            skey[c] = pack_cosine_key(sim, rank);
             sidx[c] = c;
         } else {
             if (!isfinite(nsq)) continue; // non-finite rows cannot be stored (vector_database.cpp:1771-1784)
@@ -1104,7 +1106,7 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
             const uint64_t o = static_cast<uint64_t>(q) * a.k + i;
             if (i < take) {
                 const uint32_t row = a.rank_row ? a.rank_row[key_idx(cand[sidx[i]])] : key_idx(cand[sidx[i]]);
-                a.out_scores[o] = key_score(skey[i]);
+                a.out_scores[o] = saux[sidx[i]];                    // (the row's own zero, not the key's)
                 a.out_rows[o] = global_row(a, row);
                 if (a.out_ranks) a.out_ranks[o] = key_idx(skey[i]);
             } else {
@@ -1112,7 +1114,7 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
                 a.out_rows[o] = -1;
                 if (a.out_ranks) a.out_ranks[o] = 0xffffffffu;
             }
-            if (a.out_dist) a.out_dist[o] = (i < take) ? 1.0f - key_score(skey[i]) : __builtin_inff();
+            if (a.out_dist) a.out_dist[o] = (i < take) ? 1.0f - saux[sidx[i]] : __builtin_inff();
         }
         if (threadIdx.x == 0) a.out_counts[q] = take;
     } else {
@@ -1199,7 +1201,7 @@ __global__ __launch_bounds__(256) void exact_keys_kernel(const float* rows, uint
             const double sd = denom > 0.0 ? dot / denom : 0.0;
             if (isfinite(sd)) {
                 const float sim = static_cast<float>(sd);
-                if (!(sim < threshold)) key = pack_key(sim, kidx);
+                if (!(sim < threshold)) key = pack_cosine_key(sim, kidx);   // (one zero: common.h; the re-score returns the row's own)
             }
         }
     } else {

@@ -67,7 +67,7 @@ template <int NT> __device__ __forceinline__ void group_sync() {
     else { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } // (a wave's LDS operations complete in order)
 }
 template <int METRIC, int NT>
-__device__ __forceinline__ void final_select(const SmallScanArgs& a, uint32_t q, uint32_t total, uint32_t kk,
+__device__ __forceinline__ void final_select(const SmallScanArgs& a, uint32_t q, double qn, uint32_t total, uint32_t kk,
                                              unsigned char* region, int t) {
     uint64_t* fkey = reinterpret_cast<uint64_t*>(region);                    // [1024] the survivors
     uint64_t* fcand = fkey + 1024;                                          // [1024] the candidates (>= tau)
@@ -109,7 +109,9 @@ __device__ __forceinline__ void final_select(const SmallScanArgs& a, uint32_t q,
             const uint64_t o = static_cast<uint64_t>(q) * a.k + r;
             const uint32_t rk = key_idx(mine);
             const uint32_t rowi = a.tie_rank ? a.rank_row[rk] : rk;
-            const float sim = key_score(mine);
+            float sim = key_score(mine);
+            // (the key holds the canonical zero: the row's own one comes from scoring it again, common.h)
+            if (sim == 0.0f) sim = exact_cosine_again(a.rows + static_cast<uint64_t>(rowi) * a.dim, a.queries + static_cast<uint64_t>(q) * a.dim, a.dim, qn);
             a.out_scores[o] = sim;
             a.out_rows[o] = small_global_row(a, rowi);
             if (a.out_ranks) a.out_ranks[o] = rk;
@@ -305,7 +307,7 @@ __global__ __launch_bounds__(SM_THREADS) void small_scan_kernel(SmallScanArgs a)
                     const double sd = denom > 0.0 ? dj / denom : 0.0;
                     if (isfinite(sd)) {                                  // :4273-4275
                         const float sim = static_cast<float>(sd);        // :4276
-                        if (!(sim < a.threshold)) key = pack_key(sim, rank); // :4277-4279
+                        if (!(sim < a.threshold)) key = pack_cosine_key(sim, rank); // :4277-4279 (one zero: common.h)
                     }
                 }
             } else if (isfinite(nsq)) { // non-finite rows cannot be stored (vector_database.cpp:1771-1784)
@@ -376,8 +378,8 @@ __global__ __launch_bounds__(SM_THREADS) void small_scan_kernel(SmallScanArgs a)
     SM_STAMP(6);
     const uint32_t total = gridDim.x * kk;                                // <= small_scan_max_survivors()
     // one query: the whole workgroup selects; several: wave j selects query j, the selections run side by side
-    if (nqc == 1) final_select<METRIC, SM_THREADS>(a, q0, total, kk, smem, threadIdx.x);
-    else if (static_cast<uint32_t>(wave) < nqc) final_select<METRIC, 64>(a, q0 + wave, total, kk, smem + wave * SM_FINAL_REGION, lane);
+    if (nqc == 1) final_select<METRIC, SM_THREADS>(a, q0, s_qn[0], total, kk, smem, threadIdx.x);
+    else if (static_cast<uint32_t>(wave) < nqc) final_select<METRIC, 64>(a, q0 + wave, s_qn[wave], total, kk, smem + wave * SM_FINAL_REGION, lane);
     SM_STAMP(7);
 }
 
