@@ -83,3 +83,25 @@ def build_l2_calibration_test():
     if r.returncode != 0:
         raise RuntimeError("l2_calibration_test failed to compile:\n" + r.stdout.decode())
     return exe
+
+
+def build_contract_rules_test():
+    """Compiles tests/cpp/contract_rules_test.cpp (plain g++, no GPU, no ROCm include path: yams_amd/csrc/contract_rules.h is the
+    header the kernels inline) and links it with the oracle's C restatement.  Returns the executable."""
+    import _oracle
+    _oracle.build()
+    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "contract_rules_test")
+    src = os.path.join(ROOT, "tests", "cpp", "contract_rules_test.cpp")
+    hdr = os.path.join(ROOT, "yams_amd", "csrc", "contract_rules.h")
+    pub = os.path.join(ROOT, "include", "yams_mi355x_accel.h")
+    so = os.path.join(ROOT, "oracle", "_build", "libyams_oracle.so")
+    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in (src, hdr, pub, so)):
+        return exe
+    # -ffp-contract=off, as the kernels are built: the header's fma calls are the only fused operations
+    r = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-o", exe, src, so,
+                        "-Wl,-rpath," + os.path.dirname(so), "-lm"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    if r.returncode != 0:
+        raise RuntimeError("contract_rules_test failed to compile:\n" + r.stdout.decode())
+    return exe

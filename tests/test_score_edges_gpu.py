@@ -182,3 +182,48 @@ def test_zero_plateau_across_three_shards_on_one_device(oracle):
             both_zeros_returned(r)
     finally:
         sh.close()
+
+
+def test_unused_slots_hold_the_documented_values(acc):
+    """Slots counts[q] .. k-1 of EVERY output array of yams_scan_topk_device hold score -inf / row -1 / distance +inf / rank
+    0xffffffff (contract_rules.h, write_empty_slot), written by the kernel into buffers that held other bytes: 5 rows x dim 8,
+    2 queries, k = 8, cosine and L2 with distances and ranks requested — served by the fused small scan, and by the re-score
+    behind FLAG_FORCE_EXACT.  The other entry points' padding is asserted where their results are checked and is left out
+    here: yams_scan_doc_topk_device (scores, rows, documents) by tests/test_doc_topk_gpu.py `check` and
+    tests/_doc_oracle.py `compare`; yams_scan_entity_topk_device by tests/_entity_oracle.py `compare` ("padding") and
+    tests/test_entity_gpu.py; yams_scan_merge_topk_device (scores, rows, distances) by
+    tests/test_merge_gpu.py::test_query_that_is_empty_in_every_shard."""
+    n, d, nq, k = 5, 8, 2, 8
+    rng = np.random.default_rng(11)
+    corpus = rng.standard_normal((n, d)).astype(np.float32)
+    corpus[3] = 0.0                                                 # cosine drops it; L2 keeps it with cosine 0
+    queries = rng.standard_normal((nq, d)).astype(np.float32)
+    dc, dq = acc.to_device(corpus), acc.to_device(queries)
+    view = acc.corpus_view(dc.ptr, n, d)
+    poison = np.full(nq * k * 8, 0x5a, np.uint8)
+    bufs = [acc.to_device(poison) for _ in range(5)]
+    d_s, d_r, d_n, d_d, d_k = bufs
+    try:
+        for metric in (SCAN_COSINE, _lib.SCAN_L2):
+            for flags in (0, FLAG_FORCE_EXACT):
+                for b in bufs:
+                    b.upload(poison)
+                acc.scan_topk_device(view, dq.ptr, nq, k, 0.0, metric, d_s.ptr, d_r.ptr, d_n.ptr, d_d.ptr, d_k.ptr, flags=flags)
+                acc.synchronize()
+                counts = d_n.download(np.uint32, nq)
+                scores = d_s.download(np.float32, nq * k).reshape(nq, k)
+                rows = d_r.download(np.int64, nq * k).reshape(nq, k)
+                dist = d_d.download(np.float32, nq * k).reshape(nq, k)
+                ranks = d_k.download(np.uint32, nq * k).reshape(nq, k)
+                what = (metric, flags, counts.tolist())
+                assert (counts < k).all() and counts.max() >= 1, what
+                for qi in range(nq):
+                    c = int(counts[qi])
+                    assert ((rows[qi, :c] >= 0) & (rows[qi, :c] < n)).all() and (ranks[qi, :c] == rows[qi, :c]).all(), what
+                    assert np.isneginf(scores[qi, c:]).all(), (what, scores[qi])
+                    assert (rows[qi, c:] == -1).all(), (what, rows[qi])
+                    assert np.isposinf(dist[qi, c:]).all(), (what, dist[qi])
+                    assert (ranks[qi, c:] == 0xffffffff).all(), (what, ranks[qi])
+    finally:
+        for b in bufs + [dc, dq]:
+            b.free()

@@ -7,65 +7,9 @@
 #include <string>
 
 #include "../../include/yams_mi355x_accel.h"
+#include "contract_rules.h" // the keys and the result contract's rules
 
 namespace yams_accel {
-
-// ---- order-preserving float <-> uint32 keys ----------------------------------------------------
-// Larger key == better (larger) score.  NaN maps to the top key so that a row whose fp32 filter
-// score is not trustworthy is always kept as a candidate (it is then scored exactly in fp64).
-// Key 0 is never produced and marks an empty slot.
-__host__ __device__ inline uint32_t f2ord(float f) {
-    uint32_t u;
-#if defined(__HIP_DEVICE_COMPILE__)
-    u = __float_as_uint(f);
-#else
-    __builtin_memcpy(&u, &f, 4);
-#endif
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu; // NaN
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__host__ __device__ inline float ord2f(uint32_t k) {
-    uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    float f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    f = __uint_as_float(u);
-#else
-    __builtin_memcpy(&f, &u, 4);
-#endif
-    return f;
-}
-__host__ __device__ inline uint64_t pack_key(float score, uint32_t idx) {
-    return (static_cast<uint64_t>(f2ord(score)) << 32) | static_cast<uint64_t>(0xffffffffu - idx);
-}
-// The reference orders cosine results with a FLOAT compare (sqlite_vec_backend.cpp:4218-4223, :4296-4298, :100-120):
-// -0.0f == +0.0f there, the two zeros are ONE score and the tie rank decides between them — while f2ord puts every +0.0f
-// above every -0.0f.  A cosine key therefore carries the canonical zero; the score a caller is GIVEN keeps its own sign
-// bit (the reference returns -0.0f where the fp64 quotient underflows from below), which a selection either keeps
-// beside the key or recovers by scoring the winner again (exact_cosine_again).  L2 keys (-distance: always -0.0f at
-// distance zero) have one zero only.
-__host__ __device__ inline uint64_t pack_cosine_key(float sim, uint32_t idx) {
-    return pack_key(sim == 0.0f ? 0.0f : sim, idx);
-}
-#if defined(__HIPCC__)
-// The fp64 cosine of one row as the scan kernels compute it (:4253-4276: one sequential chain per sum, element by
-// element), for a winner whose key says "zero": only the sign of the zero is news, the row is known to be valid.
-__device__ inline float exact_cosine_again(const float* x, const float* q, uint32_t dim, double qn) {
-    double nsq = 0.0, dot = 0.0;
-    for (uint32_t i = 0; i < dim; ++i) {
-        const double sv = static_cast<double>(x[i]);
-        nsq = fma(sv, sv, nsq);
-        dot = fma(sv, static_cast<double>(q[i]), dot);
-    }
-    const double denom = sqrt(nsq) * qn;
-    return static_cast<float>(denom > 0.0 ? dot / denom : 0.0);
-}
-#endif
-__host__ __device__ inline uint32_t key_idx(uint64_t k) {
-    return 0xffffffffu - static_cast<uint32_t>(k);
-}
-__host__ __device__ inline float key_score(uint64_t k) {
-    return ord2f(static_cast<uint32_t>(k >> 32));
-}
 
 // ---- dense sample scores ---------------------------------------------------------------------------
 // Layout [sample_row / 4][query][4]: in the MFMA accumulator layout a lane owns ONE query and four

@@ -34,7 +34,7 @@ namespace {
 // bytes of per-document keys (doc_key + selection keys) one slice of queries may hold: 600 queries x 1 M documents run
 // as slices of 16 queries
 constexpr uint64_t kDocKeyBudget = 256ull << 20;
-// an allow-mask that lets fewer than one row in 8 through is gathered first (compact_mask_kernel), a denser one is
+// an allow-mask that lets fewer than one row in 8 through is gathered first (launch_compact_mask), a denser one is
 // read in place
 constexpr uint64_t kSparseDivisor = 8;
 // the flags a DocumentTopK call may carry: filter-choice bits only (the call scores every allowed row in fp64 anyway)

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(kDocThreads) void doc_score_kernel(
     if (on) {
         row = rows_sel ? rows_sel[item] : item;
         if (row >= n_rows) on = false;
-        else if (!rows_sel && row_mask && !((row_mask[row >> 5] >> (row & 31)) & 1u)) on = false;
+        else if (!rows_sel && row_mask && !row_allowed(row_mask, row)) on = false;
     }
     s_row[t] = on ? static_cast<uint32_t>(row) : 0xffffffffu;
     if (t < QG) s_count[t] = 0;
@@ -106,23 +106,13 @@ __global__ __launch_bounds__(kDocThreads) void doc_score_kernel(
         __syncthreads();
     }
 
-    // scores and keys (exact_keys_kernel's cosine arm: :4267-4279)
+    // scores and keys: the fast path's rule (never the record path here)
     uint64_t key[QG];
-    const bool norm_ok = on && isfinite(nsq) && nsq > 1e-12;
-    const double rn = norm_ok ? sqrt(nsq) : 0.0;
     const uint32_t kidx = on ? (tie_rank ? tie_rank[row] : static_cast<uint32_t>(row)) : 0u;
 #pragma unroll
     for (int j = 0; j < QG; ++j) {
-        key[j] = 0;
         const uint32_t slot = slot0 + j;
-        if (norm_ok && slot < n_slots) {
-            const double denom = rn * qnorm[q0 + slot];
-            const double sd = denom > 0.0 ? dot[j] / denom : 0.0;
-            if (isfinite(sd)) {
-                const float sim = static_cast<float>(sd);
-                if (!(sim < threshold)) key[j] = pack_cosine_key(sim, kidx);   // (one zero: common.h)
-            }
-        }
+        key[j] = (on && slot < n_slots) ? fast_cosine_key(dot[j], nsq, qnorm[q0 + slot], false, threshold, kidx) : 0;
     }
     // matching rows per query (documents or not: the reference counts them before the reduction)
 #pragma unroll
@@ -216,13 +206,11 @@ __global__ __launch_bounds__(256) void doc_emit_kernel(const unsigned long long*
             float sim = key_score(dk);
             if (sim == 0.0f) sim = exact_cosine_again(rows + static_cast<uint64_t>(row) * dim, queries + static_cast<uint64_t>(q) * dim, dim, qnorm[q]);
             out_scores[o] = sim;
-            out_rows[o] = row_base + static_cast<int64_t>(row);
+            out_rows[o] = global_row_id(row_base, 0, 0, 0, row);
             if (out_docs) out_docs[o] = d;
             atomicAdd(&s_n, 1u);
         } else {
-            out_scores[o] = -__builtin_inff();
-            out_rows[o] = -1;
-            if (out_docs) out_docs[o] = YAMS_SCAN_NO_DOC;
+            write_empty_slot(o, out_scores, out_rows, nullptr, nullptr, out_docs);
         }
     }
     __syncthreads();

@@ -119,7 +119,6 @@ extern "C" yams_status_t yams_scan_entity_topk_device(yams_accel_ctx* ctx, const
         uint32_t* sel;
         YA_TRY(ws_get(ctx, "ent_rows_sel", static_cast<size_t>(corpus->n_rows) * 4, (void**)&sel));
         YA_TRY(ws_get(ctx, "ent_nsel", 8, (void**)&d_nsel));
-        YA_HIP(ctx, hipMemsetAsync(d_nsel, 0, 8, st));
         YA_HIP(ctx, launch_entity_compact(st, corpus->row_mask, corpus->n_rows, n_uniq ? d_filt + nq : nullptr,
                                           static_cast<uint32_t>(n_uniq), cols, sel, d_nsel));
         rows_sel = sel;

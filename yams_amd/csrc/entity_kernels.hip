@@ -12,7 +12,8 @@
 //
 // Launches per call:
 //   entity_qnorm_kernel     sqrt of the fp64 sum of squares of every query, in element order
-//   entity_compact_kernel   only when a row_mask or the filters restrict the rows: the ordinals some query admits
+//   compact_rows_kernel     (scan_kernels.hip) only when a row_mask or the filters restrict the rows: the ordinals some
+//                           query admits
 //   per slice of queries:
 //   entity_score_kernel     every admitted row is read from HBM once per group of QG queries (128-byte row chunks staged
 //                           through LDS with 16-byte loads, the next chunk's loads in flight while this one is summed),
@@ -22,6 +23,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "scan_launch.h"
 
 namespace yams_accel {
 
@@ -31,23 +33,6 @@ constexpr int kEntThreads = 256;        // rows per workgroup (one per thread)
 constexpr int kEntChunk = 32;           // elements of a row per LDS stage (128 bytes)
 constexpr int kEntLds = kEntChunk + 1;  // padded LDS row stride (floats): thread t reads row t, conflict-free
 constexpr int kEntLoads = kEntChunk / 4; // 16-byte loads per thread and stage: 8 lanes per row, 32 rows per pass, 8 passes
-
-// The predicate of one query over the attribute columns (three optional column equalities).  The "unset" value of a
-// column equals no filter value; a null column behind a named field never gets here (the host refuses the call).
-__device__ __forceinline__ bool entity_admits(const yams_scan_entity_filter_t& f, const uint8_t* row_type,
-                                              const uint32_t* row_node_type, const uint32_t* row_doc, uint64_t row) {
-    if ((f.fields & YAMS_SCAN_ENTITY_FILTER_TYPE) && !(f.embedding_type < YAMS_SCAN_ENTITY_TYPE_UNSET && row_type[row] == f.embedding_type)) return false;
-    if ((f.fields & YAMS_SCAN_ENTITY_FILTER_NODE_TYPE) && !(f.node_type != YAMS_SCAN_ENTITY_UNSET && row_node_type[row] == f.node_type)) return false;
-    if ((f.fields & YAMS_SCAN_ENTITY_FILTER_DOC) && !(f.doc != YAMS_SCAN_ENTITY_UNSET && row_doc[row] == f.doc)) return false;
-    return true;
-}
-
-// computeCosineSimilarity's tail (:1802-1809) and the cast of :2859: nsq = the row's sum of squares, qn = sqrt of the query's.
-__device__ __forceinline__ float entity_similarity(double dot, double nsq, double qn) {
-    const double rn = sqrt(nsq);
-    const double sd = (qn == 0.0 || rn == 0.0) ? 0.0 : dot / (qn * rn);
-    return static_cast<float>(sd);
-}
 
 // up to four consecutive floats of a row (zero-filled past `left`), as one 16-byte load when the layout allows it
 __device__ __forceinline__ float4 entity_load4(const float* src, uint32_t left, int vec4) {
@@ -77,30 +62,6 @@ __global__ __launch_bounds__(64) void entity_qnorm_kernel(const float* __restric
         s = fma(v, v, s);
     }
     qnorm[q] = sqrt(s);
-}
-
-// Row ordinals that the row_mask (nullable) lets through and that at least one of the call's distinct filters admits
-// (n_filters == 0: the filters do not restrict).  Any order: the keys carry the ordinal.
-__global__ __launch_bounds__(256) void entity_compact_kernel(const uint32_t* __restrict__ row_mask, uint64_t n_rows,
-                                                             const yams_scan_entity_filter_t* __restrict__ filters,
-                                                             uint32_t n_filters, const uint8_t* __restrict__ row_type,
-                                                             const uint32_t* __restrict__ row_node_type,
-                                                             const uint32_t* __restrict__ row_doc, uint32_t* rows_sel,
-                                                             unsigned long long* counter) {
-    const uint64_t row = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    bool on = row < n_rows && (!row_mask || ((row_mask[row >> 5] >> (row & 31)) & 1u));
-    if (on && n_filters) {
-        bool any = false;
-        for (uint32_t f = 0; f < n_filters && !any; ++f) any = entity_admits(filters[f], row_type, row_node_type, row_doc, row);
-        on = any;
-    }
-    const unsigned long long ball = __ballot(on);
-    if (ball == 0) return;
-    const int lane = threadIdx.x & 63;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(counter, static_cast<unsigned long long>(__popcll(ball)));
-    base = __shfl(base, 0);
-    if (on) rows_sel[base + __popcll(ball & ((1ull << lane) - 1ull))] = static_cast<uint32_t>(row);
 }
 
 // One thread per item (rows_sel: the compacted ordinals, bounded by *n_sel_dev; else item == row), QG queries per workgroup
@@ -204,7 +165,7 @@ __global__ __launch_bounds__(kEntThreads) void entity_score_kernel(
         unsigned long long key = 0;
         const bool a = (adm >> j) & 1u;
         if (a) {
-            const float sim = entity_similarity(dot[j], nsq, qnorm[q0 + slot]);
+            const float sim = compute_cosine_similarity(dot[j], nsq, qnorm[q0 + slot]);
             // float compare (:2862): a NaN similarity or threshold keeps nothing; -0.0f and +0.0f are one score
             if (sim >= threshold) key = pack_key(sim == 0.0f ? 0.0f : sim, static_cast<uint32_t>(row));
         }
@@ -240,22 +201,15 @@ __global__ __launch_bounds__(256) void entity_emit_kernel(const unsigned long lo
             const uint32_t r = key_idx(s);
             float sim = key_score(s);
             if (sim == 0.0f) {
-                const float* x = rows + static_cast<uint64_t>(r) * dim;
-                const float* y = queries + static_cast<uint64_t>(q) * dim;
-                double nsq = 0.0, dot = 0.0;
-                for (uint32_t e = 0; e < dim; ++e) {
-                    const double sv = static_cast<double>(x[e]);
-                    nsq = fma(sv, sv, nsq);
-                    dot = fma(static_cast<double>(y[e]), sv, dot);
-                }
-                sim = entity_similarity(dot, nsq, qnorm[q]);
+                double nsq, dot;
+                row_sums(rows + static_cast<uint64_t>(r) * dim, queries + static_cast<uint64_t>(q) * dim, dim, &nsq, &dot);
+                sim = compute_cosine_similarity(dot, nsq, qnorm[q]);
             }
             out_scores[o] = sim;
-            out_rows[o] = row_base + static_cast<int64_t>(r);
+            out_rows[o] = global_row_id(row_base, 0, 0, 0, r);
             atomicAdd(&s_n, 1u);
         } else {
-            out_scores[o] = -__builtin_inff();
-            out_rows[o] = -1;
+            write_empty_slot(o, out_scores, out_rows, nullptr, nullptr, nullptr);
         }
     }
     __syncthreads();
@@ -271,10 +225,7 @@ hipError_t launch_entity_qnorm(hipStream_t st, const float* queries, uint32_t nq
 hipError_t launch_entity_compact(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows,
                                  const yams_scan_entity_filter_t* filters, uint32_t n_filters,
                                  const yams_scan_entities_t& cols, uint32_t* rows_sel, unsigned long long* counter) {
-    if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(entity_compact_kernel, dim3(static_cast<uint32_t>((n_rows + 255) / 256)), dim3(256), 0, st, row_mask,
-                       n_rows, filters, n_filters, cols.row_type, cols.row_node_type, cols.row_doc, rows_sel, counter);
-    return hipGetLastError();
+    return launch_compact_rows(st, row_mask, n_rows, filters, n_filters, cols, rows_sel, counter);
 }
 
 hipError_t launch_entity_score(hipStream_t st, const float* rows, uint64_t n_rows, uint32_t dim, const float* queries,

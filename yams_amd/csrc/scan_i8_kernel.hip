@@ -1245,7 +1245,7 @@ __global__ __launch_bounds__(256) void i8_collect_sample_kernel(const uint32_t* 
             const int i = lane & 15;
             const uint64_t sidx = static_cast<uint64_t>(g >> 2) * 64 + 4 * (g & 3) + 16 * (i >> 2) + (i & 3);
             const uint64_t row = (sidx / I8_ROWS) * stride * I8_ROWS + (sidx % I8_ROWS);
-            const bool ok = row < n_rows && (!row_mask || ((row_mask[row >> 5] >> (row & 31u)) & 1u));
+            const bool ok = row < n_rows && (!row_mask || row_allowed(row_mask, row));
             const uint64_t rr = row < n_rows ? row : n_rows - 1;
             int dot = 0;
             for (uint32_t ch = static_cast<uint32_t>(lane >> 4); ch < nchunk; ch += 4) {
@@ -1765,7 +1765,7 @@ __global__ void i8_l2_add_special_kernel(const uint32_t* special, uint32_t n_spe
     if (q >= n_queries) return;
     for (uint32_t i = threadIdx.x; i < n_special; i += blockDim.x) {
         const uint32_t row = special[i];
-        if (row_mask && !((row_mask[row >> 5] >> (row & 31u)) & 1u)) continue;
+        if (row_mask && !row_allowed(row_mask, row)) continue;
         const uint32_t pos = atomicAdd(&list_count[q], 1u);
         if (pos < list_cap) list[static_cast<uint64_t>(q) * list_cap + pos] = pack_key(__builtin_inff(), row);
     }

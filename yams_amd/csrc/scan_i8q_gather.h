@@ -23,7 +23,7 @@ __global__ __launch_bounds__(256) void i8_log_gather_blocks_kernel(const int32_t
         q = static_cast<uint32_t>(e[0]);
         row = static_cast<uint32_t>(e[1]) + 16u * (i >> 2) + (i & 3u);
         if (row >= n_rows) return false;
-        if (row_mask && !((row_mask[row >> 5] >> (row & 31u)) & 1u)) return false;
+        if (row_mask && !row_allowed(row_mask, row)) return false;
         const int I = e[4 + i];
         const float2 m = reinterpret_cast<const float2*>(rows_meta)[row / I8_BLOCK_ROWS];
         const float2 qt = reinterpret_cast<const float2*>(q_thr)[q];

@@ -277,9 +277,8 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void scan_tiles_kernel(ScanArgs a)
 }
 
 // -------------------------------------------------------------------------------------------------
-// prep_queries: validity + fp64 norm in the reference's summation order (:4206-4211) + the
+// prep_queries: validity (query_flags) + fp64 norm in the reference's summation order (:4206-4211) + the
 // operand the MFMA pass consumes (unit-norm fp32 for cosine, raw for L2).
-//   flags: bit0 = non-finite element, bit1 = norm^2 < 1e-10 (isZeroNormEmbedding, :204-211)
 // -------------------------------------------------------------------------------------------------
 __global__ void prep_queries_kernel(const float* q, uint32_t nq, uint32_t dim, int metric,
                                     float* qprep, double* qnorm, float* qnorm_up,
@@ -300,8 +299,7 @@ __global__ void prep_queries_kernel(const float* q, uint32_t nq, uint32_t dim, i
     }
     if (threadIdx.x == 0) {
         double acc = 0.0;
-        // one sequential chain in the reference's order; fp64 cannot overflow on fp32 squares, so
-        // "every element finite" <=> "the sum is finite" (inf*inf = inf, NaN propagates)
+        // one sequential chain in the reference's order
         uint32_t i = 0;
         for (; i + 8 <= dim; i += 8) {
             float v[8];
@@ -317,10 +315,7 @@ __global__ void prep_queries_kernel(const float* q, uint32_t nq, uint32_t dim, i
             const double d = static_cast<double>(src[i]);
             acc = fma(d, d, acc);
         }
-        const bool finite = isfinite(acc);
-        uint32_t f = 0;
-        if (!finite) f |= 1u;
-        if (!(acc >= 1e-10)) f |= 2u;
+        const uint32_t f = query_flags(acc);
         s_flag = f;
         s_norm = sqrt(acc);
         qflags[qi] = f;
@@ -770,13 +765,6 @@ struct RescoreArgs {
     const uint32_t* q_over;     // nullable: != 0 -> the list of this query is incomplete
 };
 
-// local row ordinal -> the id the caller sees (yams_scan_corpus_t: row_base, stripes)
-__device__ __forceinline__ int64_t global_row(const RescoreArgs& a, uint32_t row) {
-    if (a.stripe_rows == 0) return a.row_base + static_cast<int64_t>(row);
-    const uint64_t t = row / a.stripe_rows, w = row % a.stripe_rows;
-    return a.row_base + static_cast<int64_t>((t * a.n_stripes + a.stripe_index) * a.stripe_rows + w);
-}
-
 constexpr int RS_MAX = 2048; // max candidates per query per launch
 constexpr int RS_STAGE_STRIDE = 36; // floats per staged row chunk (32 + 4 pad: b128 reads of 16 lanes hit 16 bank groups)
 
@@ -942,35 +930,24 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
                 }
             }
         } else {
-            for (uint32_t i = 0; i < dim; ++i) {
-                const double sv = static_cast<double>(x[i]);
-                const double qv = static_cast<double>(sq[i]);
-                nsq = fma(sv, sv, nsq);
-                dot = fma(sv, qv, dot);
-            }
+            row_sums(x, sq, dim, &nsq, &dot);
             if (METRIC == YAMS_SCAN_L2) l2_sum_tail(l2, x, sq, 0, dim);
         }
         const uint32_t rank = a.tie_rank ? a.tie_rank[row] : row;
         if (METRIC == YAMS_SCAN_COSINE && (a.flags & kRescoreFlagPqRerank)) {
-            // the product-quantised engine's re-rank (:4023-4040): computeCosineSimilarity(query, embedding) — each norm's own
-            // square root, 0 when either is zero, NO small-norm rule — then the threshold.  (A row with a non-finite component
-            // cannot be stored, vector_database.cpp:1771-1784: it is left out rather than ranked by a NaN.)
+            // the product-quantised engine's re-rank (:4023-4040): compute_cosine_similarity, then the threshold.  (A row with a
+            // non-finite component cannot be stored, vector_database.cpp:1771-1784: it is left out rather than ranked by a NaN.)
             if (!isfinite(nsq)) continue;
-            const double na = qn, nb = sqrt(nsq);
-            const double cs = (na == 0.0 || nb == 0.0) ? 0.0 : dot / (na * nb);
-            const float sim = static_cast<float>(cs);
+            const float sim = compute_cosine_similarity(dot, nsq, qn);
             if (sim < a.threshold || sim != sim) continue;
-            saux[c] = sim;                                          // (the key holds the canonical zero: common.h)
+            saux[c] = sim;                                          // (the key holds the canonical zero)
             skey[c] = pack_cosine_key(sim, rank);
             sidx[c] = c;
         } else if (METRIC == YAMS_SCAN_COSINE) {
-            // all elements finite <=> nsq finite (fp64 cannot overflow on fp32 squares)
-            // :4258-4269; the record path drops norm^2 < 1e-10 instead (isZeroNormEmbedding, :204-211)
-            if (!isfinite(nsq) || ((a.flags & YAMS_SCAN_FLAG_RECORD_PATH) ? nsq < 1e-10 : nsq <= 1e-12)) continue;
-            const double denom = sqrt(nsq) * qn;                    // :4271
-            const double sd = denom > 0.0 ? dot / denom : 0.0;
-            if (!isfinite(sd)) continue;                            // :4273-4275
-            const float sim = static_cast<float>(sd);               // :4276
+            // the fast path's rule in its pieces: the measurement build looks at sd between quotient and cast
+            double sd;
+            if (!fast_row_scored(nsq, (a.flags & YAMS_SCAN_FLAG_RECORD_PATH) != 0) || !fast_quotient(dot, nsq, qn, &sd)) continue;
+            const float sim = fast_cast(sd);
 #ifdef YAMS_ACCEL_MEASURE
             // bound honesty (YAMS_ACCEL_DUMP_NEEDED prints the counts): the filter's score of a re-scored candidate against its exact
             // similarity — |score - cos| <= err_bound on the bf16 / f32 tiers, cos <= score on the int8 tier (err_bound 0)
@@ -980,8 +957,8 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
                 atomicAdd(a.stat_rescored + 5, 1ull);
             }
 #endif
-            if (sim < a.threshold) continue;                        // :4277-4279
-            saux[c] = sim;                                          // (the key holds the canonical zero: common.h)
+            if (!fast_kept(sim, a.threshold)) continue;
+            saux[c] = sim;                                          // (the key holds the canonical zero)
             skey[c] = pack_cosine_key(sim, rank);
             sidx[c] = c;
         } else {
@@ -998,10 +975,7 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
                 atomicAdd(a.stat_rescored + 5, 1ull);
             }
 #endif
-            // computeCosineSimilarity (vector_database.cpp:1786-1810): sqrt each norm, 0 on zero norm
-            const double na = qn, nb = sqrt(nsq);
-            const double cs = (na == 0.0 || nb == 0.0) ? 0.0 : dot / (na * nb);
-            saux[c] = static_cast<float>(cs);
+            saux[c] = compute_cosine_similarity(dot, nsq, qn);     // (reported beside the distance)
             skey[c] = pack_key(-dist, rank); // ascending distance == descending -dist
             sidx[c] = c;
         }
@@ -1107,14 +1081,12 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
             if (i < take) {
                 const uint32_t row = a.rank_row ? a.rank_row[key_idx(cand[sidx[i]])] : key_idx(cand[sidx[i]]);
                 a.out_scores[o] = saux[sidx[i]];                    // (the row's own zero, not the key's)
-                a.out_rows[o] = global_row(a, row);
+                a.out_rows[o] = global_row_id(a.row_base, a.stripe_rows, a.n_stripes, a.stripe_index, row);
                 if (a.out_ranks) a.out_ranks[o] = key_idx(skey[i]);
+                if (a.out_dist) a.out_dist[o] = 1.0f - saux[sidx[i]];
             } else {
-                a.out_scores[o] = -__builtin_inff();
-                a.out_rows[o] = -1;
-                if (a.out_ranks) a.out_ranks[o] = 0xffffffffu;
+                write_empty_slot(o, a.out_scores, a.out_rows, a.out_dist, a.out_ranks, nullptr);
             }
-            if (a.out_dist) a.out_dist[o] = (i < take) ? 1.0f - saux[sidx[i]] : __builtin_inff();
         }
         if (threadIdx.x == 0) a.out_counts[q] = take;
     } else {
@@ -1129,7 +1101,7 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
                 const uint64_t o = static_cast<uint64_t>(q) * a.k + outn;
                 const uint32_t row = a.rank_row ? a.rank_row[key_idx(cand[sidx[i]])] : key_idx(cand[sidx[i]]);
                 a.out_scores[o] = cs;
-                a.out_rows[o] = global_row(a, row);
+                a.out_rows[o] = global_row_id(a.row_base, a.stripe_rows, a.n_stripes, a.stripe_index, row);
                 if (a.out_dist) a.out_dist[o] = -key_score(skey[i]);
                 if (a.out_ranks) a.out_ranks[o] = key_idx(skey[i]);
                 ++outn;
@@ -1138,13 +1110,8 @@ __global__ __launch_bounds__(512) void rescore_select_kernel(RescoreArgs a) {
             a.out_counts[q] = outn;
         }
         __syncthreads();
-        for (uint32_t i = s_outn + threadIdx.x; i < a.k; i += blockDim.x) {
-            const uint64_t o = static_cast<uint64_t>(q) * a.k + i;
-            a.out_scores[o] = -__builtin_inff();
-            a.out_rows[o] = -1;
-            if (a.out_dist) a.out_dist[o] = __builtin_inff();
-            if (a.out_ranks) a.out_ranks[o] = 0xffffffffu;
-        }
+        for (uint32_t i = s_outn + threadIdx.x; i < a.k; i += blockDim.x)
+            write_empty_slot(static_cast<uint64_t>(q) * a.k + i, a.out_scores, a.out_rows, a.out_dist, a.out_ranks, nullptr);
     }
 }
 
@@ -1177,7 +1144,7 @@ __global__ __launch_bounds__(256) void exact_keys_kernel(const float* rows, uint
         row = rows_sel[slot_i];
     } else {
         if (row >= n_rows) return;
-        if (row_mask && !((row_mask[row >> 5] >> (row & 31)) & 1u)) {
+        if (row_mask && !row_allowed(row_mask, row)) {
             keys[static_cast<uint64_t>(slot) * key_stride + slot_i] = 0;
             return;
         }
@@ -1196,14 +1163,8 @@ __global__ __launch_bounds__(256) void exact_keys_kernel(const float* rows, uint
     uint64_t key = 0;
     const uint32_t kidx = tie_rank ? tie_rank[row] : static_cast<uint32_t>(row);
     if (METRIC == YAMS_SCAN_COSINE) {
-        if (isfinite(nsq) && ((flags & YAMS_SCAN_FLAG_RECORD_PATH) ? nsq >= 1e-10 : nsq > 1e-12)) {
-            const double denom = sqrt(nsq) * qnorm[q];
-            const double sd = denom > 0.0 ? dot / denom : 0.0;
-            if (isfinite(sd)) {
-                const float sim = static_cast<float>(sd);
-                if (!(sim < threshold)) key = pack_cosine_key(sim, kidx);   // (one zero: common.h; the re-score returns the row's own)
-            }
-        }
+        // (the key's one zero; the re-score returns the row's own)
+        key = fast_cosine_key(dot, nsq, qnorm[q], (flags & YAMS_SCAN_FLAG_RECORD_PATH) != 0, threshold, kidx);
     } else {
         if (isfinite(nsq)) {
             const double dd = l2.root();
@@ -1213,12 +1174,21 @@ __global__ __launch_bounds__(256) void exact_keys_kernel(const float* rows, uint
     keys[static_cast<uint64_t>(slot) * key_stride + slot_i] = key;
 }
 
-// Row ordinals of the set bits of an allow-mask (any order: the keys carry the row / rank).
-__global__ __launch_bounds__(256) void compact_mask_kernel(const uint32_t* row_mask, uint64_t n_rows,
-                                                           uint32_t* rows_sel,
+// Row ordinals that the row_mask (nullable) lets through and that at least one of the entity filters admits (n_filters == 0:
+// no filters, the columns are not read).  Any order: the keys carry the row / rank.
+__global__ __launch_bounds__(256) void compact_rows_kernel(const uint32_t* __restrict__ row_mask, uint64_t n_rows,
+                                                           const yams_scan_entity_filter_t* __restrict__ filters,
+                                                           uint32_t n_filters, const uint8_t* __restrict__ row_type,
+                                                           const uint32_t* __restrict__ row_node_type,
+                                                           const uint32_t* __restrict__ row_doc, uint32_t* rows_sel,
                                                            unsigned long long* counter) {
     const uint64_t row = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const bool on = row < n_rows && ((row_mask[row >> 5] >> (row & 31)) & 1u);
+    bool on = row < n_rows && (!row_mask || row_allowed(row_mask, row));
+    if (on && n_filters) {
+        bool any = false;
+        for (uint32_t f = 0; f < n_filters && !any; ++f) any = entity_admits(filters[f], row_type, row_node_type, row_doc, row);
+        on = any;
+    }
     const unsigned long long ball = __ballot(on);
     if (ball == 0) return;
     const int lane = threadIdx.x & 63;
@@ -1320,12 +1290,8 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(MergeArgs a) {
         a.out_counts[q] = outn;
     }
     __syncthreads();
-    for (uint32_t i = s_outn + threadIdx.x; i < a.k; i += blockDim.x) {
-        const uint64_t d = static_cast<uint64_t>(q) * a.k + i;
-        a.out_scores[d] = -__builtin_inff();
-        a.out_rows[d] = -1;
-        if (a.out_dist) a.out_dist[d] = __builtin_inff();
-    }
+    for (uint32_t i = s_outn + threadIdx.x; i < a.k; i += blockDim.x)
+        write_empty_slot(static_cast<uint64_t>(q) * a.k + i, a.out_scores, a.out_rows, a.out_dist, nullptr, nullptr);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1572,13 +1538,14 @@ hipError_t launch_exact_keys(hipStream_t st, int metric, const float* rows, uint
     return hipSuccess;
 }
 
-hipError_t launch_compact_mask(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows,
+hipError_t launch_compact_rows(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows,
+                               const yams_scan_entity_filter_t* filters, uint32_t n_filters, const yams_scan_entities_t& cols,
                                uint32_t* rows_sel, unsigned long long* counter) {
     if (n_rows == 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(counter, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(compact_mask_kernel, dim3(static_cast<uint32_t>((n_rows + 255) / 256)),
-                       dim3(256), 0, st, row_mask, n_rows, rows_sel, counter);
+    hipLaunchKernelGGL(compact_rows_kernel, dim3(static_cast<uint32_t>((n_rows + 255) / 256)), dim3(256), 0, st, row_mask,
+                       n_rows, filters, n_filters, cols.row_type, cols.row_node_type, cols.row_doc, rows_sel, counter);
     LAUNCH_CHECK();
     return hipSuccess;
 }

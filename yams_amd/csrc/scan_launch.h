@@ -164,8 +164,15 @@ hipError_t launch_exact_keys(hipStream_t st, int metric, const float* rows, uint
                              const uint32_t* rows_sel, uint64_t n_sel, const uint32_t* qmap,
                              uint32_t n_slots, float threshold, uint32_t flags, uint64_t* keys,
                              uint64_t key_stride);
-hipError_t launch_compact_mask(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows,
+// The ordinals of the rows that the row_mask (nullable) lets through and that at least one of the n_filters entity filters
+// admits (0: none to apply), gathered into rows_sel in any order; *counter = how many (zeroed here first).
+hipError_t launch_compact_rows(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows,
+                               const yams_scan_entity_filter_t* filters, uint32_t n_filters, const yams_scan_entities_t& cols,
                                uint32_t* rows_sel, unsigned long long* counter);
+inline hipError_t launch_compact_mask(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows, uint32_t* rows_sel,
+                                      unsigned long long* counter) {
+    return launch_compact_rows(st, row_mask, n_rows, nullptr, 0, yams_scan_entities_t{nullptr, nullptr, nullptr}, rows_sel, counter);
+}
 hipError_t launch_topk_keys(hipStream_t st, const uint64_t* keys, uint64_t key_stride,
                             uint32_t n_per_slot, uint32_t n_slots, uint32_t keep, uint64_t* work,
                             const uint64_t** result, uint64_t* result_stride);

@@ -31,12 +31,6 @@ constexpr int SM_THREADS = 256;
 constexpr int SM_PASS_CHUNKS = 4;             // chunks of 32 dims (128 B of each of the wave's 64 rows = 8 KiB) staged per pass
 constexpr int SM_RING_BYTES = SM_PASS_CHUNKS * 8 * 1024; // per wave
 
-__device__ __forceinline__ int64_t small_global_row(const SmallScanArgs& a, uint32_t row) {
-    if (a.stripe_rows == 0) return a.row_base + static_cast<int64_t>(row);
-    const uint64_t t = row / a.stripe_rows, w = row % a.stripe_rows;
-    return a.row_base + static_cast<int64_t>((t * a.n_stripes + a.stripe_index) * a.stripe_rows + w);
-}
-
 // Selection by RANK COUNTING instead of sorting.  Keys are unique (they carry the row's tie rank) or zero (empty
 // slot), so the place of a key in the descending order is the number of keys greater than it: every thread counts
 // that for its own key(s) against the list in LDS — broadcast reads, 16 bytes = two keys at a time, no bank
@@ -110,10 +104,10 @@ __device__ __forceinline__ void final_select(const SmallScanArgs& a, uint32_t q,
             const uint32_t rk = key_idx(mine);
             const uint32_t rowi = a.tie_rank ? a.rank_row[rk] : rk;
             float sim = key_score(mine);
-            // (the key holds the canonical zero: the row's own one comes from scoring it again, common.h)
+            // (the key holds the canonical zero: the row's own one comes from scoring it again)
             if (sim == 0.0f) sim = exact_cosine_again(a.rows + static_cast<uint64_t>(rowi) * a.dim, a.queries + static_cast<uint64_t>(q) * a.dim, a.dim, qn);
             a.out_scores[o] = sim;
-            a.out_rows[o] = small_global_row(a, rowi);
+            a.out_rows[o] = global_row_id(a.row_base, a.stripe_rows, a.n_stripes, a.stripe_index, rowi);
             if (a.out_ranks) a.out_ranks[o] = rk;
             if (a.out_dist) a.out_dist[o] = 1.0f - sim;
         } else {
@@ -122,12 +116,8 @@ __device__ __forceinline__ void final_select(const SmallScanArgs& a, uint32_t q,
         }
     }
     if (METRIC == YAMS_SCAN_COSINE) {
-        for (uint32_t r = take + t; r < a.k; r += NT) {
-            const uint64_t o = static_cast<uint64_t>(q) * a.k + r;
-            a.out_scores[o] = -__builtin_inff(); a.out_rows[o] = -1;
-            if (a.out_ranks) a.out_ranks[o] = 0xffffffffu;
-            if (a.out_dist) a.out_dist[o] = __builtin_inff();
-        }
+        for (uint32_t r = take + t; r < a.k; r += NT)
+            write_empty_slot(static_cast<uint64_t>(q) * a.k + r, a.out_scores, a.out_rows, a.out_dist, a.out_ranks, nullptr);
         if (t == 0) a.out_counts[q] = take;
         return;
     }
@@ -144,19 +134,15 @@ __device__ __forceinline__ void final_select(const SmallScanArgs& a, uint32_t q,
         const uint32_t rk = key_idx(mine);
         const uint32_t rowi = a.tie_rank ? a.rank_row[rk] : rk;
         a.out_scores[o] = fcs[r];
-        a.out_rows[o] = small_global_row(a, rowi);
+        a.out_rows[o] = global_row_id(a.row_base, a.stripe_rows, a.n_stripes, a.stripe_index, rowi);
         if (a.out_dist) a.out_dist[o] = -key_score(mine);
         if (a.out_ranks) a.out_ranks[o] = rk;
         atomicAdd(&s_cnt[2], 1u);
     }
     group_sync<NT>();
     const uint32_t outn = s_cnt[2];
-    for (uint32_t rr = outn + t; rr < a.k; rr += NT) {
-        const uint64_t o = static_cast<uint64_t>(q) * a.k + rr;
-        a.out_scores[o] = -__builtin_inff(); a.out_rows[o] = -1;
-        if (a.out_dist) a.out_dist[o] = __builtin_inff();
-        if (a.out_ranks) a.out_ranks[o] = 0xffffffffu;
-    }
+    for (uint32_t rr = outn + t; rr < a.k; rr += NT)
+        write_empty_slot(static_cast<uint64_t>(q) * a.k + rr, a.out_scores, a.out_rows, a.out_dist, a.out_ranks, nullptr);
     if (t == 0) a.out_counts[q] = outn;
 }
 
@@ -191,7 +177,7 @@ __global__ __launch_bounds__(SM_THREADS) void small_scan_kernel(SmallScanArgs a)
     const uint32_t row_raw = blockIdx.x * SM_THREADS + threadIdx.x;
     bool live = row_raw < a.n_rows;
     const uint32_t row = live ? row_raw : a.n_rows - 1;                   // (a valid address for the staged loads)
-    if (live && a.row_mask && !((a.row_mask[row >> 5] >> (row & 31)) & 1u)) live = false;
+    if (live && a.row_mask && !row_allowed(a.row_mask, row)) live = false;
     double nsq = 0.0, dot[QB], dsq[QB];
 #pragma unroll
     for (int j = 0; j < QB; ++j) { dot[j] = 0.0; dsq[j] = 0.0; }
@@ -240,11 +226,8 @@ __global__ __launch_bounds__(SM_THREADS) void small_scan_kernel(SmallScanArgs a)
                 for (int e = 0; e < 4; ++e) { const double d = static_cast<double>(vv[e]); acc = fma(d, d, acc); }
             }
         }
-        uint32_t f = 0;
-        if (!isfinite(acc)) f |= 1u;             // a non-finite element (fp64 cannot overflow on fp32 squares)
-        if (!(acc >= 1e-10)) f |= 2u;            // isZeroNormEmbedding, :204-211
         s_qn[lane] = sqrt(acc);
-        if (blockIdx.x == 0 && static_cast<uint32_t>(lane) < nqc) a.qflags[q0 + lane] = f;
+        if (blockIdx.x == 0 && static_cast<uint32_t>(lane) < nqc) a.qflags[q0 + lane] = query_flags(acc);
     }
     if (wave_live) {
         // lane L = row L of the wave: block (L >> 3) of a chunk, row-in-8 (L & 7), piece p in slot (p + rho(L)) & 7
@@ -301,22 +284,12 @@ __global__ __launch_bounds__(SM_THREADS) void small_scan_kernel(SmallScanArgs a)
         float aux = 0.f;
         if (live) {
             if (METRIC == YAMS_SCAN_COSINE) {
-                // :4258-4269 (the record path drops norm^2 < 1e-10 instead, isZeroNormEmbedding :204-211)
-                if (isfinite(nsq) && ((a.flags & YAMS_SCAN_FLAG_RECORD_PATH) ? nsq >= 1e-10 : nsq > 1e-12)) {
-                    const double denom = sqrt(nsq) * qn;                 // :4271
-                    const double sd = denom > 0.0 ? dj / denom : 0.0;
-                    if (isfinite(sd)) {                                  // :4273-4275
-                        const float sim = static_cast<float>(sd);        // :4276
-                        if (!(sim < a.threshold)) key = pack_cosine_key(sim, rank); // :4277-4279 (one zero: common.h)
-                    }
-                }
+                key = fast_cosine_key(dj, nsq, qn, (a.flags & YAMS_SCAN_FLAG_RECORD_PATH) != 0, a.threshold, rank);
             } else if (isfinite(nsq)) { // non-finite rows cannot be stored (vector_database.cpp:1771-1784)
                 const double dd = sqrt(qj);
                 if (isfinite(dd)) {
                     key = pack_key(-static_cast<float>(dd), rank);       // ascending distance == descending -dist
-                    // computeCosineSimilarity (vector_database.cpp:1786-1810): sqrt each norm, 0 on zero norm
-                    const double nb = sqrt(nsq);
-                    aux = static_cast<float>((qn == 0.0 || nb == 0.0) ? 0.0 : dj / (qn * nb));
+                    aux = compute_cosine_similarity(dj, nsq, qn);       // (reported beside the distance)
                 }
             }
         }
