@@ -772,7 +772,71 @@ YAMS_ACCEL_API yams_status_t yams_cluster_assign_device(
     const uint8_t* centroid_empty, uint32_t* out_assign, double* out_distance);
 
 /* ------------------------------------------------------------------------------------------ */
-/* SHA-256                                                                                      */
+/* The semantic-neighbour graph: exact top-K self-join of the document-level embeddings         */
+/* ------------------------------------------------------------------------------------------ */
+/* EmbeddingService::updateSemanticNeighborGraphUnlocked (src/daemon/components/EmbeddingService.cpp) scores, for every
+ * source document, every other document-level embedding and writes the best semanticTopK (default 8, :385) as
+ * `semantic_neighbor` edges: N^2 * D scalar fp64 multiply-adds on one core (:612-648 the streaming branch, :856-1076 the
+ * whole-corpus branch).  This entry is that loop; the shell around it is include/yams_accel/semantic_graph.hpp.
+ * The contract, restated from EmbeddingService.cpp:
+ *   inverse norm (:405-415)  norm = an fp64 chain of x * x in element order; inv = norm <= 0 ? 0.0f : float(1.0 / sqrt(norm)).
+ *             A row with inv <= 0 is not part of the corpus (:876-878, :527): never a candidate, no neighbours as a source.
+ *   similarity (:417-431)  dot = an fp64 chain of double(a[i]) * double(b[i]) in element order;
+ *             sim = float((dot * double(inv_source)) * double(inv_neighbour)), in that operand order.
+ *   admission (:626-632, :991-997)  adaptive mode (no explicit threshold): sim <= 0.0f is dropped, both zeros go; explicit
+ *             mode: sim < threshold is dropped (at threshold 0.0f both -0.0f and +0.0f stay).
+ *   self (:619, :985)  the source never lists itself: the row index differs.  Another row with identical bits is listed.
+ *   order (:464-470, :949-954)  similarity descending by the float compare (the two zeros are ONE score; the returned score
+ *             keeps its sign bit), then document hash ascending: tie_rank[row] = the rank of the row's hash, a permutation
+ *             of [0, n); without one, row order.
+ *   result  the min-replacement loop (:637-646, :1001-1010) keeps exactly the best K under that strict total order; they are
+ *             returned sorted (:760, :1017).  The effective threshold (:761-762, :1018-1019) is the explicit one or the
+ *             last kept similarity: every kept row passes it, so the result is the sorted list of at most K rows.
+ *   diagnostics  pairs_scored = similarityPairCount, pairs_admitted = candidateNeighborCount (summed over the sources).
+ * What the reference leaves undefined is refused with YAMS_ERR_INVALID_ARG and nothing written: a non-finite element (NaN
+ * similarities in a comparator that does not order them; inserts are validated finite, src/vector/vector_database.cpp:
+ * 1771-1784) and a row whose float inverse norm is +inf (every element a denormal: 0 * inf).  A finite, denormal inverse
+ * norm (a row of +-FLT_MAX / 4: inv = 4.2e-39) is served.  Results equal the CPU loop bit for bit: no chain is split.
+ * Limits: n < 2^31, dim <= YAMS_GRAPH_MAX_DIM, k <= YAMS_GRAPH_MAX_K: beyond, YAMS_ERR_UNSUPPORTED.  k == 0, n < 2 or
+ * n_sources == 0: YAMS_OK, an empty result (the early return at :890; nothing written, *out_diag zeroed).  dim == 0, null
+ * rows or null outputs: YAMS_ERR_INVALID_ARG.
+ *   rows          device [n][dim] fp32, raw (any float alignment)
+ *   tie_rank      device [n] uint32, nullable.  Not a permutation of [0, n): YAMS_ERR_INVALID_ARG (found on the device).
+ *   source_rows   device [n_sources] uint32, nullable = every row in row order (n_sources is then taken as n); indices may
+ *                 repeat and come in any order; an index >= n: YAMS_ERR_INVALID_ARG (found on the device).
+ *   flags         YAMS_GRAPH_FLAG_EXPLICIT_THRESHOLD: `threshold` is the explicit one (any finite value; the adapter
+ *                 clamps to [0, 1] as :398 does); otherwise adaptive mode and `threshold` is ignored.  A non-finite
+ *                 threshold in explicit mode, or an unknown flag: YAMS_ERR_INVALID_ARG.
+ *   out_rows      device [n_sources][k] uint32, best first; unused slots 0xffffffff
+ *   out_sims      device [n_sources][k] fp32; unused slots -inf
+ *   out_counts    device [n_sources] uint32
+ *   out_inv_norm  device [n] fp32, nullable: the inverse norms (what the host caches in SemanticCorpusEntry)
+ *   out_diag      host, nullable
+ * Work: n_sources * n * dim fp64 multiply-adds in tiles of 128 sources x 64 candidates; when the source tiles alone would
+ * leave CUs idle the candidates are dealt to `stripes` workgroups per source tile and a merge kernel joins their lists.
+ * No n^2-sized buffer: the workspace is O(n) + n_sources * stripes * k keys.  One 4-byte read-back (the refusal flags)
+ * sits between the inverse-norm pass and the pairs.  The call synchronises the context's stream before returning. */
+#define YAMS_GRAPH_MAX_DIM 4096u
+#define YAMS_GRAPH_MAX_K 64u
+#define YAMS_GRAPH_FLAG_EXPLICIT_THRESHOLD 1u
+typedef struct yams_graph_diag {
+    uint32_t stripes;        /* candidate stripes per source tile (1 = no merge needed) */
+    uint32_t source_tiles;   /* tiles of 128 sources */
+    uint64_t pairs_scored;   /* similarityPairCount */
+    uint64_t pairs_admitted; /* candidateNeighborCount */
+} yams_graph_diag_t;
+YAMS_ACCEL_API yams_status_t yams_graph_semantic_neighbors_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint32_t* tie_rank,
+    const uint32_t* source_rows, uint64_t n_sources, uint32_t k, uint32_t flags, float threshold,
+    uint32_t* out_rows, float* out_sims, uint32_t* out_counts, float* out_inv_norm, yams_graph_diag_t* out_diag);
+/* The same over host memory: rows, tie_rank, source_rows and the four output arrays are host arrays. */
+YAMS_ACCEL_API yams_status_t yams_graph_semantic_neighbors_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint32_t* tie_rank,
+    const uint32_t* source_rows, uint64_t n_sources, uint32_t k, uint32_t flags, float threshold,
+    uint32_t* out_rows, float* out_sims, uint32_t* out_counts, float* out_inv_norm, yams_graph_diag_t* out_diag);
+
+/* ------------------------------------------------------------------------------------------ */
+/* SHA-256                                                                                   */
 /* ------------------------------------------------------------------------------------------ */
 /* Digest n_msgs byte ranges of one device buffer: message i = data[offsets[i] .. +lengths[i]).
  * offsets/lengths are DEVICE arrays; digests is device [n_msgs][32] (raw bytes, big-endian words
@@ -1123,6 +1187,26 @@ typedef struct yams_topology_cluster_v1 {
     void (*free_clusters)(void* self, uint32_t* membership, float* centroids);
     void (*free_assignment)(void* self, uint32_t* assign, double* distance);
 } yams_topology_cluster_v1;
+
+/* The semantic-neighbour graph (yams_graph_semantic_neighbors_host) for a host that holds the document-level embeddings
+ * in its own memory.  A separate interface, version 1, served by yams_plugin_get_interface and NOT listed in the
+ * manifest, for the reason given at vector_doc_scan_v1.  Host memory in, host memory out. */
+#define YAMS_IFACE_SEMANTIC_GRAPH_V1 "semantic_graph_v1"
+#define YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION 1u
+typedef struct yams_semantic_graph_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION */
+    void* self;
+    /* The best k neighbours of every source over rows [n][dim]; tie_rank [n] and source_rows [n_sources] nullable as in
+     * yams_graph_semantic_neighbors_device.  *out_rows [S][k], *out_sims [S][k], *out_counts [S] (S = the number of
+     * sources) and *out_inv_norm [n] (nullable: not wanted) are allocated by the plugin (release with free_neighbors);
+     * out_diag nullable.  Statuses and limits of the flat entry; an empty result (k == 0, n < 2, no sources) gives null
+     * arrays. */
+    yams_status_t (*neighbors)(void* self, const float* rows, uint64_t n, uint32_t dim, const uint32_t* tie_rank,
+                               const uint32_t* source_rows, uint64_t n_sources, uint32_t k, uint32_t flags, float threshold,
+                               uint32_t** out_rows, float** out_sims, uint32_t** out_counts, float** out_inv_norm,
+                               yams_graph_diag_t* out_diag);
+    void (*free_neighbors)(void* self, uint32_t* rows, float* sims, uint32_t* counts, float* inv_norm);
+} yams_semantic_graph_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

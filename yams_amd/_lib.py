@@ -206,6 +206,26 @@ class TopologyClusterV1(C.Structure):  # topology_cluster_v1 (served by get_inte
 CLUSTER_MAX_DIM, CLUSTER_MAX_K = 4096, 65536     # YAMS_CLUSTER_MAX_DIM / _MAX_K
 
 
+class GraphDiag(C.Structure):  # yams_graph_diag_t
+    _fields_ = [("stripes", C.c_uint32), ("source_tiles", C.c_uint32), ("pairs_scored", C.c_uint64), ("pairs_admitted", C.c_uint64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class SemanticGraphV1(C.Structure):  # semantic_graph_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("neighbors", C.CFUNCTYPE(ST, vp, f32p, C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float,
+                                  C.POINTER(u32p), C.POINTER(f32p), C.POINTER(u32p), C.POINTER(f32p), C.POINTER(GraphDiag))),
+        ("free_neighbors", C.CFUNCTYPE(None, vp, u32p, f32p, u32p, f32p)),
+    ]
+
+
+GRAPH_MAX_DIM, GRAPH_MAX_K = 4096, 64            # YAMS_GRAPH_MAX_DIM / _MAX_K
+GRAPH_FLAG_EXPLICIT_THRESHOLD = 1
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -261,6 +281,7 @@ EXPORTS = [
     "yams_scan_topk_device", "yams_scan_topk_host", "yams_scan_merge_topk_device", "yams_scan_pq_topk_device",
     "yams_scan_doc_topk_device", "yams_scan_entity_topk_device",
     "yams_cluster_kmeans_device", "yams_cluster_kmeans_host", "yams_cluster_assign_device",
+    "yams_graph_semantic_neighbors_device", "yams_graph_semantic_neighbors_host",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -350,6 +371,9 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
     L.yams_cluster_kmeans_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u32p, u32p]
     L.yams_cluster_kmeans_host.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, u32p, u32p]
     L.yams_cluster_assign_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
+    for fn in (L.yams_graph_semantic_neighbors_device, L.yams_graph_semantic_neighbors_host):
+        fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp,
+                       C.POINTER(GraphDiag)]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

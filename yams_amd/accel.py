@@ -548,6 +548,63 @@ class Accel:
                     b.free()
         return a, dist
 
+    def semantic_neighbors_device(self, rows_ptr: int, n: int, dim: int, k: int, out_rows_ptr: int, out_sims_ptr: int,
+                                  out_counts_ptr: int, tie_rank_ptr: int | None = None, source_rows_ptr: int | None = None,
+                                  n_sources: int = 0, threshold: float | None = None, out_inv_norm_ptr: int | None = None) -> dict:
+        """yams_graph_semantic_neighbors_device over device arrays; threshold=None is the adaptive mode.  Returns the
+        diagnostics {stripes, source_tiles, pairs_scored, pairs_admitted}."""
+        diag = _lib.GraphDiag()
+        flags = 0 if threshold is None else _lib.GRAPH_FLAG_EXPLICIT_THRESHOLD
+        self._check(self.L.yams_graph_semantic_neighbors_device(self.ctx, rows_ptr, n, dim, tie_rank_ptr, source_rows_ptr, n_sources, k,
+                                                                flags, 0.0 if threshold is None else threshold, out_rows_ptr,
+                                                                out_sims_ptr, out_counts_ptr, out_inv_norm_ptr, C.byref(diag)))
+        return diag.as_dict()
+
+    def semantic_neighbors(self, rows: np.ndarray, k: int = 8, tie_rank: np.ndarray | None = None,
+                           source_rows: np.ndarray | None = None, threshold: float | None = None, host_entry: bool = False):
+        """The semantic-neighbour graph's pair loop (EmbeddingService::updateSemanticNeighborGraphUnlocked) over host rows
+        [n][dim]: for every source (every row, or source_rows) its best k other rows.  Returns (rows [S][k] uint32 with
+        0xffffffff in unused slots, sims [S][k] float32 with -inf there, counts [S] uint32, inv_norm [n] float32, diag).
+        threshold=None is the adaptive mode (sim <= 0 dropped).  host_entry=True goes through
+        yams_graph_semantic_neighbors_host instead of uploading here."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        assert x.ndim == 2
+        n, dim = x.shape
+        tr = None if tie_rank is None else np.ascontiguousarray(tie_rank, dtype=np.uint32)
+        sr = None if source_rows is None else np.ascontiguousarray(source_rows, dtype=np.uint32)
+        S = n if sr is None else len(sr)
+        o_r = np.full((S, k), 0xffffffff, np.uint32); o_s = np.full((S, k), -np.inf, np.float32)
+        o_c = np.zeros(S, np.uint32); o_i = np.zeros(n, np.float32)
+        flags = 0 if threshold is None else _lib.GRAPH_FLAG_EXPLICIT_THRESHOLD
+        thr = 0.0 if threshold is None else threshold
+        diag = _lib.GraphDiag()
+        if host_entry:
+            self._check(self.L.yams_graph_semantic_neighbors_host(
+                self.ctx, x.ctypes.data, n, dim, tr.ctypes.data if tr is not None else None, sr.ctypes.data if sr is not None else None, S,
+                k, flags, thr, o_r.ctypes.data, o_s.ctypes.data, o_c.ctypes.data, o_i.ctypes.data, C.byref(diag)))
+            return o_r, o_s, o_c, o_i, diag.as_dict()
+        bufs = [self.to_device(a) if a is not None and a.size else None for a in (x, tr, sr)]
+        d_x, d_t, d_s = bufs
+        outs = [self.alloc(S * k * 4 + 16), self.alloc(S * k * 4 + 16), self.alloc(S * 4 + 16), self.alloc(n * 4 + 16)]
+        try:
+            self._check(self.L.yams_graph_semantic_neighbors_device(
+                self.ctx, d_x.ptr if d_x else None, n, dim, d_t.ptr if d_t else None, d_s.ptr if d_s else None, S, k, flags, thr,
+                outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr, C.byref(diag)))
+            if k and n >= 2 and S:
+                o_r = outs[0].download(np.uint32, S * k).reshape(S, k)
+                o_s = outs[1].download(np.float32, S * k).reshape(S, k)
+                o_c = outs[2].download(np.uint32, S)
+                o_i = outs[3].download(np.float32, n)
+        finally:
+            for b in bufs + outs:
+                if b is not None:
+                    b.free()
+        return o_r, o_s, o_c, o_i, diag.as_dict()
+
+    def semantic_neighbors_host(self, rows: np.ndarray, k: int = 8, **kw):
+        """semantic_neighbors through yams_graph_semantic_neighbors_host (host arrays in, host arrays out)."""
+        return self.semantic_neighbors(rows, k, host_entry=True, **kw)
+
     def scan_pq_topk(self, corpus: ScanCorpus, codes: np.ndarray, luts: np.ndarray, queries: np.ndarray, k: int, threshold: float = -1.0,
                      rerank_factor: int = 2, tie_keys: np.ndarray | None = None, row_of_index: np.ndarray | None = None,
                      candidates: np.ndarray | None = None, sum_lanes: int = 1) -> ScanResult:

@@ -122,6 +122,20 @@ YAMS_RULE float compute_cosine_similarity(double dot, double nsq_row, double qn)
     return static_cast<float>((qn == 0.0 || rn == 0.0) ? 0.0 : dot / (qn * rn));
 }
 
+// ---- the semantic-neighbour graph (src/daemon/components/EmbeddingService.cpp) -------------------------------------
+// inverseNorm (:405-415) from the row's fp64 sum of squares: 0 for a zero row, else the fp64 quotient rounded to FLOAT.
+YAMS_RULE float graph_inverse_norm(double nsq) {
+    return nsq <= 0.0 ? 0.0f : static_cast<float>(1.0 / std::sqrt(nsq));
+}
+// cosineSimilarity's tail (:430): (dot * invSource) * invNeighbour in fp64, in THAT order, then the cast.
+YAMS_RULE float graph_similarity(double dot, float inv_source, float inv_neighbour) {
+    return static_cast<float>((dot * static_cast<double>(inv_source)) * static_cast<double>(inv_neighbour));
+}
+// Admission (:626-632, :991-997): an explicit threshold drops sim < threshold; without one, sim <= 0 (both zeros) goes.
+YAMS_RULE bool graph_admits(float sim, bool explicit_threshold, float threshold) {
+    return explicit_threshold ? !(sim < threshold) : !(sim <= 0.0f);
+}
+
 // ---- the allow-mask: bit (row & 31) of word row / 32 (yams_scan_corpus_t.row_mask, non-null here) -----------------
 YAMS_RULE bool row_allowed(const uint32_t* row_mask, uint64_t row) {
     return (row_mask[row >> 5] >> (row & 31)) & 1u;

@@ -1254,6 +1254,43 @@ void tc_free_assignment(void*, uint32_t* assign, double* distance) { std::free(a
 yams_topology_cluster_v1 g_topology_cluster = {YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION, nullptr, GUARDED(tc_kmeans), GUARDED(tc_assign),
                                                GUARDED(tc_free_clusters), GUARDED(tc_free_assignment)};
 
+// ---- semantic_graph_v1: the semantic-neighbour graph over host memory (yams_graph_semantic_neighbors_host) ------------------
+yams_status_t sg_neighbors(void*, const float* rows, uint64_t n, uint32_t dim, const uint32_t* tie_rank, const uint32_t* source_rows,
+                           uint64_t n_sources, uint32_t k, uint32_t flags, float threshold, uint32_t** out_rows, float** out_sims,
+                           uint32_t** out_counts, float** out_inv_norm, yams_graph_diag_t* out_diag) {
+    NEED_INIT();
+    if (!out_rows || !out_sims || !out_counts) return YAMS_ERR_INVALID_ARG;
+    *out_rows = nullptr; *out_sims = nullptr; *out_counts = nullptr;
+    if (out_inv_norm) *out_inv_norm = nullptr;
+    if (out_diag) std::memset(out_diag, 0, sizeof *out_diag);
+    const uint64_t S = source_rows ? n_sources : n;
+    // the limits bound the arrays allocated here; every other check is the flat entry's
+    if (n >= (1ull << 31) || S >= (1ull << 31) || dim > YAMS_GRAPH_MAX_DIM || k > YAMS_GRAPH_MAX_K) return YAMS_ERR_UNSUPPORTED;
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    if (k == 0 || n < 2 || S == 0)      // an empty result: null arrays (the flat entry still judges flags and threshold)
+        return yams_graph_semantic_neighbors_host(w.v, rows, n, dim, tie_rank, source_rows, n_sources, k, flags, threshold, nullptr, nullptr,
+                                                  nullptr, nullptr, out_diag);
+    const size_t slots = static_cast<size_t>(S) * k;
+    auto* r = static_cast<uint32_t*>(std::malloc(slots * 4));
+    auto* s = static_cast<float*>(std::malloc(slots * 4));
+    auto* c = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(S) * 4));
+    auto* iv = out_inv_norm ? static_cast<float*>(std::malloc(static_cast<size_t>(n) * 4)) : nullptr;
+    auto drop = [&] { std::free(r); std::free(s); std::free(c); std::free(iv); };
+    if (!r || !s || !c || (out_inv_norm && !iv)) { drop(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    const yams_status_t st = yams_graph_semantic_neighbors_host(w.v, rows, n, dim, tie_rank, source_rows, n_sources, k, flags, threshold, r, s, c,
+                                                                iv, out_diag);
+    if (st != YAMS_OK) { drop(); return st; }
+    *out_rows = r; *out_sims = s; *out_counts = c;
+    if (out_inv_norm) *out_inv_norm = iv;
+    return YAMS_OK;
+}
+
+void sg_free_neighbors(void*, uint32_t* rows, float* sims, uint32_t* counts, float* inv_norm) {
+    std::free(rows); std::free(sims); std::free(counts); std::free(inv_norm);
+}
+
+yams_semantic_graph_v1 g_semantic_graph = {YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION, nullptr, GUARDED(sg_neighbors), GUARDED(sg_free_neighbors)};
+
 // ---- content_hash_v1 --------------------------------------------------------------------------
 // Every call leases one of the plugin's work contexts (own stream, own workspace), so hashing, chunking
 // and searches of different host threads overlap on the device instead of queueing on one mutex.
@@ -1762,6 +1799,10 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
     if (std::strcmp(iface_id, YAMS_IFACE_TOPOLOGY_CLUSTER_V1) == 0) { // (not in the manifest: see the header)
         if (version < 1 || version > YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
         *out_iface = &g_topology_cluster; return YAMS_PLUGIN_OK;
+    }
+    if (std::strcmp(iface_id, YAMS_IFACE_SEMANTIC_GRAPH_V1) == 0) { // (not in the manifest: see the header)
+        if (version < 1 || version > YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
+        *out_iface = &g_semantic_graph; return YAMS_PLUGIN_OK;
     }
     if (std::strcmp(iface_id, YAMS_IFACE_CONTENT_HASH_V1) == 0) {
         if (version < 1 || version > YAMS_IFACE_CONTENT_HASH_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
