@@ -55,13 +55,20 @@ ScanPlan make_plan(uint64_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, bool 
     // 2.7x what the proof needs, the chance of a list too short to prove is ~1e-7 per query)
     const uint32_t need_rank = (2 * p.kprime + p.kprime / 2 + 32 + p.sample_stride - 1) / p.sample_stride;
     p.tau_rank = std::min<uint32_t>(std::max<uint32_t>(16, round_up(need_rank, 16)), kRescoreMax);
+    // (groups that lie wholly in the padding behind the last row of a sampled ragged last tile have the maximum -inf: they
+    // count towards n_groups but not towards the ranks a finite threshold needs.  4097 .. 4351 rows on the 256-row tiles,
+    // k <= 10: 272 groups, 257 .. 271 of them real, tau_rank 272 — the threshold was -inf, every row was listed, the lists
+    // were cut at 4096 and EVERY query of every batch took the exhaustive pass.)
+    const uint64_t padding = static_cast<uint64_t>(p.n_tiles) * p.tile_rows - n_rows;
+    const bool last_tile_sampled = p.n_tiles > 0 && (p.n_tiles - 1) % p.sample_stride == 0;
+    const uint32_t real_groups = p.n_groups - (last_tile_sampled ? static_cast<uint32_t>(padding / kGroupRows) : 0u);
     // (a list longer than what can be re-scored does not hurt the proof: the best kRescoreMax bounds are re-scored and the next
     // one is the proof's threshold; a list cut short by a threshold the sample put too high does)
-    if (depth >= 2 && p.tau_rank * 2 <= 256 && p.n_groups >= p.tau_rank * 2) p.tau_rank *= 2;
+    if (depth >= 2 && p.tau_rank * 2 <= 256 && real_groups >= p.tau_rank * 2) p.tau_rank *= 2;
     if (depth >= 1) p.kprime = kRescoreMax;
     // expected list length tau_rank * stride (relative spread ~1/sqrt(tau_rank)): 4x is > 15 sigma
     uint64_t cap = std::max<uint64_t>(4096, 4ull * p.tau_rank * p.sample_stride);
-    if (p.n_groups < p.tau_rank) cap = std::max<uint64_t>(cap, n_rows); // threshold is -inf
+    if (real_groups < p.tau_rank) cap = std::max<uint64_t>(cap, n_rows); // threshold is -inf
     cap = std::min<uint64_t>(cap, std::max<uint64_t>(n_rows, 4096));
     p.list_cap = round_up(static_cast<uint32_t>(cap), 256);
     return p;
