@@ -15,8 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
-def _kernels(src):
-    """{mangled kernel name: [assembly lines]} of the product build of one translation unit."""
+def _assembly(src):
+    """The gfx950 assembly (lines) of the product build of one translation unit."""
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
         cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
@@ -24,9 +24,13 @@ def _kernels(src):
                os.path.join(ROOT, "yams_amd", "csrc", src), "-o", out]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
         assert r.returncode == 0, r.stdout[-3000:]
-        text = open(out).read().splitlines()
+        return open(out).read().splitlines()
+
+
+def _kernels(src, text=None):
+    """{mangled kernel name: [assembly lines]} of the product build of one translation unit."""
     kernels, cur = {}, None
-    for line in text:
+    for line in text if text is not None else _assembly(src):
         m = re.match(r"^(_ZN10yams_accel\w+):", line)
         if m:
             cur = m.group(1); kernels[cur] = []
@@ -35,6 +39,46 @@ def _kernels(src):
             if "s_endpgm" in line:
                 cur = None
     return kernels
+
+
+def _metadata(text):
+    """{mangled kernel name: {key: int}} of the integer fields of the amdhsa.kernels metadata the assembly carries."""
+    meta, cur = {}, None
+    for line in text:
+        if line.startswith("  - ."):
+            cur = {}
+        m = re.match(r"^(?:  - |    )\.(\w+):\s+(\S+)$", line)
+        if cur is None or not m:
+            continue
+        if m.group(1) == "name":
+            meta[m.group(2)] = cur
+        elif m.group(2).isdigit():
+            cur[m.group(1)] = int(m.group(2))
+    return meta
+
+
+@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+@pytest.mark.parametrize("src,kernel,lds,sgpr_spills", [("kmeans_kernels.hip", "kmeans_assign_kernel", 25088, (0, 0)),
+                                                        ("semgraph_kernels.hip", "semgraph_pairs_kernel", 25152, (0, 6))])
+def test_the_fp64_tile_kernels_keep_three_waves_their_lds_and_no_scratch(src, kernel, lds, sgpr_spills):
+    """kmeans_assign_kernel and semgraph_pairs_kernel share their hot loop (fp64_tile.h) as an inlined function, and how that
+    function is shaped moves the register allocation.  Both forms of both kernels (vector and scalar loads) must stay where they
+    were measured: at most 168 registers — a SIMD has 512 registers per lane, handed out in granules of 8, so 168 is the most
+    that leaves three waves per SIMD (3 x 168 = 504; 176 would leave two) — no scratch (private segment 0, no spill, no
+    scratch_ instruction) and the static LDS of the two operand buffers (+ 64 bytes of counters in the pairs kernel).
+    sgpr_spills = (vector form, scalar form): scalar registers parked in lanes of a vector register, never in memory; the
+    scalar-load form of the pairs kernel has had six since it was written, the other three forms none."""
+    text = _assembly(src)
+    meta = {k: v for k, v in _metadata(text).items() if kernel in k}
+    bodies = {k: v for k, v in _kernels(src, text).items() if kernel in k}
+    assert len(meta) == 2 and set(meta) == set(bodies), (list(meta), list(bodies))
+    assert {("ILb1E" in k) for k in meta} == {True, False}, list(meta)       # <VEC = true> and <VEC = false>
+    for name, m in meta.items():
+        assert m["private_segment_fixed_size"] == 0, (name, m)
+        assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] <= sgpr_spills["ILb0E" in name], (name, m)
+        assert not any("scratch_" in l for l in bodies[name]), name
+        assert m["group_segment_fixed_size"] == lds, (name, m)
+        assert m.get("agpr_count", 0) == 0 and m["vgpr_count"] <= 168, (name, m)
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")

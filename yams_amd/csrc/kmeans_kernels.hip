@@ -9,10 +9,8 @@
 //   :341-478                                              runKMeans: farthest-first initialisation, Lloyd iterations, empty-cluster repair
 //   src/topology/topology_build_utils.h:27-56             meanEmbedding: fp32 running sum over the members in list order, / float(count)
 //
-// Exactness: the product of two floats is exact in fp64, so fma(a, b, acc) == acc + a * b bit for bit; every chain below walks
-// its elements in the reference's order (the dimension for a distance, the member list for a mean) and no chain is ever split.
-// A chunk that reaches past `dim` is filled with +0.0f: a chain that starts at +0.0 can never hold -0.0 (x + y is -0.0 only when
-// both are), so adding the exact product +0.0 leaves every value, NaN and infinities included, as it was.
+// Exactness: every chain walks its elements in the reference's order (the dimension for a distance — fp64_tile.h has the
+// argument — and the member list for a mean) and is never split.
 // na / nb are per-row / per-centroid: computed once by the same chain, kept as (sum, sqrt(sum)).
 //
 // Kernels:
@@ -27,6 +25,8 @@
 #include <cfloat>
 
 #include "common.h"
+#include "fp64_tile.h"
+#include "row_walk.h"
 
 namespace yams_accel {
 
@@ -34,14 +34,7 @@ namespace {
 
 constexpr int kKmThreads = 256;
 constexpr int kKmMaxDim = 4096;          // YAMS_CLUSTER_MAX_DIM: one centroid fits the 16 KiB LDS stage of pick / centroid
-// row-walk kernels (norm, rowdist): one row per thread, 16 elements of 256 rows per LDS stage
-constexpr int kRwChunk = 16;
-constexpr int kRwLds = kRwChunk + 1;     // padded stride (floats): thread t walks row t conflict-free
-// assignment kernel: 128 rows x 64 centroids per tile, 8 x 4 fp64 accumulators per lane, 8 dimensions per LDS stage
-constexpr int kAsRows = 128, kAsCents = 64, kAsChunk = 8;
-constexpr int kAsRB = 8, kAsCB = 4;      // register block: rows x centroids per lane (16 x 16 lanes)
-constexpr int kAsLdA = kAsRows + 2;      // LDS strides in doubles: rows stay 16-byte aligned, and the two half-chunks a wave
-constexpr int kAsLdB = kAsCents + 2;     // stores (four dimensions apart) fall on different banks
+static_assert(kKmThreads == kRwRows && kKmThreads == kTileThreads, "the row walk and the tile are built for this workgroup");
 
 // cosineDistance's tail (:300-304) from the three sums; ra / rb = sqrt(na) / sqrt(nb).  std::clamp(v, lo, hi) is
 // (v < lo) ? lo : (hi < v) ? hi : v: a NaN passes through.
@@ -50,19 +43,6 @@ __device__ __forceinline__ double km_distance(double dot, double na, double ra, 
     const double c = dot / (ra * rb);
     const double cl = (c < -1.0) ? -1.0 : ((1.0 < c) ? 1.0 : c);
     return 1.0 - cl;
-}
-
-// Stages elements [d0, d0 + 16) of rows [base, base + 256) into tile (zero-filled past n / dim): 16 lanes read the 64
-// contiguous bytes of one row.
-__device__ __forceinline__ void km_stage_rows(const float* __restrict__ x, uint64_t n, uint32_t dim, uint64_t base, uint32_t d0,
-                                              float (*tile)[kRwLds]) {
-    const int t = threadIdx.x, dc = t & 15;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int r = (t >> 4) + 16 * i;
-        const uint64_t row = base + r;
-        tile[r][dc] = (row < n && d0 + dc < dim) ? x[row * dim + d0 + dc] : 0.0f;
-    }
 }
 
 // normalized (:307-319) of the `dim` floats in v (LDS), written to out (global) and back to v; then (nb, sqrt(nb)) of the
@@ -97,16 +77,15 @@ __device__ __forceinline__ void km_normalize_store(float* v, uint32_t dim, float
 // norms[r] = (sum of squares, its sqrt), fp64, element by element.  *nonfinite |= 1 when a sum is not finite.
 __global__ __launch_bounds__(kKmThreads) void kmeans_norm_kernel(const float* __restrict__ x, uint64_t n, uint32_t dim,
                                                                  double2* __restrict__ norms, uint32_t* __restrict__ nonfinite) {
-    __shared__ float tile[kKmThreads][kRwLds];
+    __shared__ RowWalkTile tile;
     const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kKmThreads;
     const int t = threadIdx.x;
     double s = 0.0;
     for (uint32_t d0 = 0; d0 < dim; d0 += kRwChunk) {
         __syncthreads();
-        km_stage_rows(x, n, dim, base, d0, tile);
+        rw_stage_rows(x, n, dim, base, d0, tile);
         __syncthreads();
-#pragma unroll
-        for (int e = 0; e < kRwChunk; ++e) { const double a = static_cast<double>(tile[t][e]); s = fma(a, a, s); }
+        s = rw_add_squares(tile, s);
     }
     if (base + t < n) {
         norms[base + t] = make_double2(s, sqrt(s));
@@ -125,7 +104,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_rowdist_kernel(const float*
                                                                     uint32_t fixed, const uint8_t* __restrict__ selected,
                                                                     double* __restrict__ min_dist, double* __restrict__ part_val,
                                                                     uint32_t* __restrict__ part_idx, double* __restrict__ out_dist) {
-    __shared__ float tile[kKmThreads][kRwLds];
+    __shared__ RowWalkTile tile;
     __shared__ double r_val[kKmThreads / 64];
     __shared__ uint32_t r_idx[kKmThreads / 64];
     const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kKmThreads;
@@ -137,7 +116,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_rowdist_kernel(const float*
     double dot = 0.0;
     for (uint32_t d0 = 0; d0 < dim; d0 += kRwChunk) {
         __syncthreads();
-        km_stage_rows(x, n, dim, base, d0, tile);
+        rw_stage_rows(x, n, dim, base, d0, tile);
         __syncthreads();
 #pragma unroll
         for (int e = 0; e < kRwChunk; ++e) {
@@ -215,9 +194,8 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_pick_kernel(const double* _
 }
 
 // nearestCentroid (:321-336) of every row.  Grid: one workgroup per 128 rows; it walks the centroid tiles in ascending order.
-// Lane (ty, tx) of 16 x 16 owns rows ty*8 .. +7 and, in each tile, centroids tx*4 .. +3: 32 fp64 chains, each walking the
-// dimension sequentially.  Both operand chunks (8 dimensions, converted to fp64) are staged in LDS, double-buffered: the
-// next chunk's global loads are issued before this chunk's chains run, and stored to the other buffer after them.
+// Lane (ty, tx) of 16 x 16 owns rows ty*8 .. +7 and, in each tile, centroids tx*4 .. +3: the 32 chains of tile_chains
+// (fp64_tile.h), A = the rows, B = the tile's centroids.
 // best = (distance, index) with "first strictly smaller wins": inside a lane the centroids come in ascending order; across
 // the 16 lanes of a row the reduction is lexicographic (smaller distance, then smaller index), which picks the lowest index
 // among the minima exactly as the sequential loop does.  A NaN distance never passes `<`; a row no centroid wins keeps
@@ -230,90 +208,34 @@ __global__ __launch_bounds__(kKmThreads, 2) void kmeans_assign_kernel(const floa
                                                                    const uint8_t* __restrict__ skip, uint32_t* __restrict__ membership,
                                                                    uint32_t* __restrict__ changed, uint32_t* __restrict__ out_assign,
                                                                    double* __restrict__ out_dist) {
-    __shared__ __attribute__((aligned(16))) double sa[2][kAsChunk][kAsLdA];
-    __shared__ __attribute__((aligned(16))) double sb[2][kAsChunk][kAsLdB];
+    __shared__ __attribute__((aligned(16))) TileLdsA sa;
+    __shared__ __attribute__((aligned(16))) TileLdsB sb;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const uint64_t row0 = static_cast<uint64_t>(blockIdx.x) * kAsRows;
-    // staging roles: A — row t/2, dimensions (t%2)*4 .. +3 of the chunk; B — centroid t/4, dimensions (t%4)*2 .. +1
-    const int ar = t >> 1, ad = (t & 1) * 4, br = t >> 2, bd = (t & 3) * 2;
-    const uint64_t a_row = row0 + ar;
+    const uint64_t row0 = static_cast<uint64_t>(blockIdx.x) * kTileA;
+    const uint64_t a_row = row0 + tile_a_row(t);
     const bool a_live = a_row < n;
     const float* a_src = x + (a_live ? a_row : 0) * dim;
-    const uint32_t n_chunks = (dim + kAsChunk - 1) / kAsChunk;
 
-    double best_d[kAsRB];
-    uint32_t best_c[kAsRB];
+    double best_d[kTileRB];
+    uint32_t best_c[kTileRB];
 #pragma unroll
-    for (int i = 0; i < kAsRB; ++i) { best_d[i] = DBL_MAX; best_c[i] = 0; }
+    for (int i = 0; i < kTileRB; ++i) { best_d[i] = DBL_MAX; best_c[i] = 0; }
 
-    for (uint32_t c0 = 0; c0 < k; c0 += kAsCents) {
-        const uint32_t b_cent = c0 + br;
+    for (uint32_t c0 = 0; c0 < k; c0 += kTileB) {
+        const uint32_t b_cent = c0 + tile_b_row(t);
         const bool b_live = b_cent < k;
         const float* b_src = cents + static_cast<uint64_t>(b_live ? b_cent : 0) * dim;
-        float fa[4], fb[2];
-        auto load = [&](uint32_t d0) {
-            if (VEC) {   // dim % 4 == 0 and 16-byte aligned bases: whole vectors are inside the row
-                const float4 v = (a_live && d0 + ad < dim) ? *reinterpret_cast<const float4*>(a_src + d0 + ad) : make_float4(0.f, 0.f, 0.f, 0.f);
-                fa[0] = v.x; fa[1] = v.y; fa[2] = v.z; fa[3] = v.w;
-                const float2 w = (b_live && d0 + bd < dim) ? *reinterpret_cast<const float2*>(b_src + d0 + bd) : make_float2(0.f, 0.f);
-                fb[0] = w.x; fb[1] = w.y;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) fa[e] = (a_live && d0 + ad + e < dim) ? a_src[d0 + ad + e] : 0.0f;
-#pragma unroll
-                for (int e = 0; e < 2; ++e) fb[e] = (b_live && d0 + bd + e < dim) ? b_src[d0 + bd + e] : 0.0f;
-            }
-        };
-        auto store = [&](int buf) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sa[buf][ad + e][ar] = static_cast<double>(fa[e]);
-#pragma unroll
-            for (int e = 0; e < 2; ++e) sb[buf][bd + e][br] = static_cast<double>(fb[e]);
-        };
-        double acc[kAsRB][kAsCB];
-#pragma unroll
-        for (int i = 0; i < kAsRB; ++i)
-#pragma unroll
-            for (int j = 0; j < kAsCB; ++j) acc[i][j] = 0.0;
-
-        __syncthreads();          // the previous tile's last chunk has been read by every lane
-        load(0);
-        store(0);
-        __syncthreads();
-        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-            const int buf = ch & 1;
-            const bool more = ch + 1 < n_chunks;
-            if (more) load((ch + 1) * kAsChunk);
-#pragma unroll 2      // (a full unroll hoists every LDS read of the chunk: 330 registers)
-            for (int e = 0; e < kAsChunk; ++e) {
-                double a[kAsRB], b[kAsCB];
-#pragma unroll
-                for (int i = 0; i < kAsRB; i += 2) {
-                    const double2 v = *reinterpret_cast<const double2*>(&sa[buf][e][ty * kAsRB + i]);
-                    a[i] = v.x; a[i + 1] = v.y;
-                }
-#pragma unroll
-                for (int j = 0; j < kAsCB; j += 2) {
-                    const double2 v = *reinterpret_cast<const double2*>(&sb[buf][e][tx * kAsCB + j]);
-                    b[j] = v.x; b[j + 1] = v.y;
-                }
-#pragma unroll
-                for (int i = 0; i < kAsRB; ++i)
-#pragma unroll
-                    for (int j = 0; j < kAsCB; ++j) acc[i][j] = fma(a[i], b[j], acc[i][j]);
-            }
-            if (more) store(buf ^ 1);
-            __syncthreads();
-        }
+        double acc[kTileRB][kTileCB];
+        tile_chains<VEC>(sa, sb, a_src, a_live, b_src, b_live, dim, acc);
         // the distance formula and the running minimum, centroids of the lane in ascending order
 #pragma unroll
-        for (int j = 0; j < kAsCB; ++j) {
-            const uint32_t c = c0 + tx * kAsCB + j;
+        for (int j = 0; j < kTileCB; ++j) {
+            const uint32_t c = c0 + tx * kTileCB + j;
             if (c >= k || (skip && skip[c])) continue;
             const double2 nb = cent_norm[c];
 #pragma unroll
-            for (int i = 0; i < kAsRB; ++i) {
-                const uint64_t r = row0 + ty * kAsRB + i;
+            for (int i = 0; i < kTileRB; ++i) {
+                const uint64_t r = row0 + ty * kTileRB + i;
                 const double2 na = row_norm[r < n ? r : n - 1];     // (re-read per tile: 16 registers the chains keep)
                 const double d = km_distance(acc[i][j], na.x, na.y, nb.x, nb.y);
                 if (d < best_d[i]) { best_d[i] = d; best_c[i] = c; }
@@ -322,7 +244,7 @@ __global__ __launch_bounds__(kKmThreads, 2) void kmeans_assign_kernel(const floa
     }
     // the 16 lanes of a row: lexicographic (distance, index) minimum
 #pragma unroll
-    for (int i = 0; i < kAsRB; ++i) {
+    for (int i = 0; i < kTileRB; ++i) {
         double d = best_d[i];
         uint32_t c = best_c[i];
 #pragma unroll
@@ -331,7 +253,7 @@ __global__ __launch_bounds__(kKmThreads, 2) void kmeans_assign_kernel(const floa
             const uint32_t oc = __shfl_xor(c, o);
             if (od < d || (od == d && oc < c)) { d = od; c = oc; }
         }
-        const uint64_t r = row0 + ty * kAsRB + i;
+        const uint64_t r = row0 + ty * kTileRB + i;
         if (tx == 0 && r < n) {
             if (membership) {
                 if (membership[r] != c) { membership[r] = c; *changed = 1u; }
@@ -452,12 +374,11 @@ hipError_t launch_kmeans_assign(hipStream_t st, const float* x, uint64_t n, uint
                                 const double2* cent_norm, uint32_t k, const uint8_t* skip, uint32_t* membership, uint32_t* changed,
                                 uint32_t* out_assign, double* out_dist) {
     if (n == 0) return hipSuccess;
-    const bool vec = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(cents) & 7) == 0;
-    if (vec)
-        kmeans_assign_kernel<true><<<km_blocks(n, kAsRows), kKmThreads, 0, st>>>(x, n, dim, row_norm, cents, cent_norm, k, skip, membership,
+    if (tile_vec_loads(dim, x, cents))
+        kmeans_assign_kernel<true><<<km_blocks(n, kTileA), kKmThreads, 0, st>>>(x, n, dim, row_norm, cents, cent_norm, k, skip, membership,
                                                                                 changed, out_assign, out_dist);
     else
-        kmeans_assign_kernel<false><<<km_blocks(n, kAsRows), kKmThreads, 0, st>>>(x, n, dim, row_norm, cents, cent_norm, k, skip, membership,
+        kmeans_assign_kernel<false><<<km_blocks(n, kTileA), kKmThreads, 0, st>>>(x, n, dim, row_norm, cents, cent_norm, k, skip, membership,
                                                                                  changed, out_assign, out_dist);
     return hipGetLastError();
 }
