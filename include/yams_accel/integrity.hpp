@@ -89,7 +89,7 @@ public:
         for (size_t i = 0; i < n; ++i) all[i] = i;
         yams_status_t st = verify(all);
         if (st == YAMS_ERR_UNSUPPORTED) {
-            // A lone or dominating long chain in the set (plugin.cpp, chains_suit_the_device): intact data must not be
+            // A lone or dominating long chain in the set (plugin_host.h, chains_suit_the_device): intact data must not be
             // reported corrupt for that.  The chains above 1 MiB go one at a time, the rest is a set the device takes.
             std::vector<size_t> small;
             for (size_t i = 0; i < n; ++i) if (lens[i] > (size_t(1) << 20)) chain(i); else small.push_back(i);

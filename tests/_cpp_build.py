@@ -105,3 +105,23 @@ def build_contract_rules_test():
     if r.returncode != 0:
         raise RuntimeError("contract_rules_test failed to compile:\n" + r.stdout.decode())
     return exe
+
+
+def build_plugin_host_test():
+    """Compiles tests/cpp/plugin_host_test.cpp (plain g++, no GPU, no ROCm include path: yams_amd/csrc/plugin_host.h is the
+    plugin door's host logic) with AddressSanitizer and UBSan: the program has its own main and hands the header heap
+    arrays of exactly the contracted lengths, so an access past one ends the run.  Returns the executable."""
+    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "plugin_host_test")
+    src = os.path.join(ROOT, "tests", "cpp", "plugin_host_test.cpp")
+    deps = [src, os.path.join(ROOT, "include", "yams_mi355x_accel.h")] + \
+        [os.path.join(ROOT, "yams_amd", "csrc", h) for h in ("plugin_host.h", "contract_rules.h")]
+    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
+        return exe
+    r = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra",
+                        "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    if r.returncode != 0:
+        raise RuntimeError("plugin_host_test failed to compile:\n" + r.stdout.decode())
+    return exe

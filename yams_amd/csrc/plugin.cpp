@@ -1,15 +1,15 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// three interface vtables (vector_scan_v1, content_hash_v1, chunker_v1) written to the
+// seven interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
+// semantic_graph_v1, content_hash_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
 // yams_plugin_get_manifest_json, then yams_plugin_get_interface(id, version, &vtable).
-#include <algorithm>
+// What the door computes on the host alone (configuration, row / mask / rank dealing, hit packing, hex) is plugin_host.h.
 #include <algorithm>
 #include <atomic>
-#include <cctype>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -19,8 +19,6 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <numeric>
-#include <set>
 #include <shared_mutex>
 #include <sstream>
 #include <string>
@@ -28,11 +26,13 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "plugin_host.h"
 
 // The eight entry points and their return codes are declared in include/yams_mi355x_accel.h exactly as
 // the reference's include/yams/plugins/abi.h:18-34 declares them (no local restatement here).
 
 namespace {
+using namespace yams_accel::plugin_host;
 
 // No exception may cross the C ABI (model_provider_v1.h:44-49; the reference's own plugins wrap every entry point,
 // plugins/onnx/model_provider.cpp:51,94,105): every function pointer of the three vtables is the guarded form of
@@ -244,51 +244,44 @@ struct ShardStore {
     }
 };
 
+// A ya_malloc'd device array with ONE owner (move-only): freed on its device when the owner goes or takes another.
+template <typename T> struct DevArray {
+    int device = 0;
+    T* p = nullptr;
+    DevArray() = default;
+    DevArray(DevArray&& o) noexcept : device(o.device), p(o.p) { o.p = nullptr; }
+    DevArray& operator=(DevArray&& o) noexcept { std::swap(device, o.device); std::swap(p, o.p); return *this; }
+    ~DevArray() { if (p) { (void)hipSetDevice(device); (void)hipFree(p); } }
+    bool alloc(int dev, size_t bytes) {          // (on an empty owner; the caller has made `dev` current)
+        device = dev;
+        return yams_accel::ya_malloc(reinterpret_cast<void**>(&p), bytes) == hipSuccess;
+    }
+    operator T*() const { return p; }
+};
+
 // The host's product-quantiser index of a corpus (SimeonPqIndexState, sqlite_vec_backend.cpp:48-62), on the corpus's device:
 // codes, the rank of every code's tie-break key, and the mirror row behind every key index.
 struct PqIndex {
-    uint8_t* codes = nullptr; uint32_t* tie_rank = nullptr; uint32_t* key_row = nullptr;
-    uint64_t n = 0; uint32_t m = 0; int device = 0;
-    void release() {
-        if (codes || tie_rank || key_row) (void)hipSetDevice(device);
-        if (codes) (void)hipFree(codes);
-        if (tie_rank) (void)hipFree(tie_rank);
-        if (key_row) (void)hipFree(key_row);
-        codes = nullptr; tie_rank = key_row = nullptr; n = 0; m = 0;
-    }
+    DevArray<uint8_t> codes; DevArray<uint32_t> tie_rank, key_row;
+    uint64_t n = 0; uint32_t m = 0;
+    void release() { *this = PqIndex(); }
 };
 
 // The row -> document map of a corpus (vector_doc_scan_v1.corpus_set_documents), on the corpus's device.
 struct DocMap {
     std::vector<uint32_t> row_doc;   // host copy: rows appended after the map was set are NO_DOC (padded per search)
-    uint32_t* d_row_doc = nullptr; uint32_t* d_doc_rank = nullptr;
-    uint64_t n_rows = 0; uint32_t n_docs = 0; int device = 0;
-    void release() {
-        if (d_row_doc || d_doc_rank) (void)hipSetDevice(device);
-        if (d_row_doc) (void)hipFree(d_row_doc);
-        if (d_doc_rank) (void)hipFree(d_doc_rank);
-        d_row_doc = d_doc_rank = nullptr; n_rows = 0; n_docs = 0;
-        std::vector<uint32_t>().swap(row_doc);
-    }
+    DevArray<uint32_t> d_row_doc, d_doc_rank;
+    uint64_t n_rows = 0; uint32_t n_docs = 0;
+    void release() { *this = DocMap(); }
 };
 
 // The attribute columns of an entity corpus (vector_entity_scan_v1.corpus_set_attributes), on the corpus's device.  The host
 // copies cover the rows set so far; rows appended later carry the "unset" values (padded per search).
 struct EntityCols {
     std::vector<uint8_t> type; std::vector<uint32_t> node, doc;
-    uint8_t* d_type = nullptr; uint32_t* d_node = nullptr; uint32_t* d_doc = nullptr;
-    uint64_t n_rows = 0; int device = 0;
-    void release_device() {
-        if (d_type || d_node || d_doc) (void)hipSetDevice(device);
-        if (d_type) (void)hipFree(d_type);
-        if (d_node) (void)hipFree(d_node);
-        if (d_doc) (void)hipFree(d_doc);
-        d_type = nullptr; d_node = d_doc = nullptr;
-    }
-    void release() {
-        release_device(); n_rows = 0;
-        std::vector<uint8_t>().swap(type); std::vector<uint32_t>().swap(node); std::vector<uint32_t>().swap(doc);
-    }
+    DevArray<uint8_t> d_type; DevArray<uint32_t> d_node, d_doc;
+    uint64_t n_rows = 0;
+    void release() { *this = EntityCols(); }
 };
 
 struct Corpus {
@@ -360,143 +353,14 @@ struct PluginState {
     uint64_t next_id = 1;
     std::atomic<uint64_t> searches{0}, hashes{0}, chunk_calls{0}, refused_chains{0}, deferred_chains{0};
 };
-PluginState g;
+PluginState& g = *new PluginState;   // never destroyed: when a host exits without yams_plugin_shutdown, the corpora's DevArrays must
+                                     // not reach hipFree from a static destructor (the runtime may have gone before them)
 
 const char kManifest[] =
     "{\"name\":\"yams_mi355x_accel\",\"version\":\"" YAMS_ACCEL_VERSION_STRING "\",\"abi\":1,"
     "\"description\":\"MI355X (gfx950) exact vector scan, SHA-256 and content-defined chunking\","
     "\"interfaces\":[{\"id\":\"vector_scan_v1\",\"version\":1},"
     "{\"id\":\"content_hash_v1\",\"version\":1},{\"id\":\"chunker_v1\",\"version\":3}]}";
-
-// ---- the plugin's configuration: a strict reader of ONE flat JSON object ----------------------------------------------------
-// {"key": "string" | integer | [integers] | true | false | null | {...} | [...]}: keys the plugin does not know are skipped
-// (whatever their value, nested or not); a key it knows with a value of the wrong TYPE, an enumerated value it does not
-// list, or text that is not a JSON object fails yams_plugin_init — a host's typo must not silently serve another arithmetic
-// (round 5 read its keys with strstr: {"shadows":"none","note":"both"} enabled both shadows).
-struct Config {
-    std::map<std::string, std::string> strings;
-    std::map<std::string, long> ints;
-    std::map<std::string, std::vector<long>> int_lists;
-    std::set<std::string> other;       // keys present with a value of another type (booleans, null, objects, nested arrays, floats)
-    std::string error;                 // non-empty: the text did not parse
-
-    static void ws(const char*& p) { while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r') ++p; }
-    static bool str(const char*& p, std::string& out) {
-        if (*p != '"') return false;
-        out.clear();
-        for (++p; *p && *p != '"'; ++p) {
-            if (*p == '\\') { ++p; if (!*p) return false; out.push_back(*p == 'n' ? '\n' : (*p == 't' ? '\t' : *p)); }
-            else out.push_back(*p);
-        }
-        if (*p != '"') return false;
-        ++p;
-        return true;
-    }
-    static bool integer(const char*& p, long& v) {
-        char* e = nullptr;
-        v = std::strtol(p, &e, 10);
-        if (e == p || *e == '.' || *e == 'e' || *e == 'E') return false;
-        p = e;
-        return true;
-    }
-    static bool skip(const char*& p, int depth = 0) {   // any JSON value
-        ws(p);
-        if (depth > 32) return false;
-        std::string t;
-        if (*p == '"') return str(p, t);
-        if (*p == '{' || *p == '[') {
-            const char close = *p == '{' ? '}' : ']';
-            const bool object = *p == '{';
-            ++p; ws(p);
-            if (*p == close) { ++p; return true; }
-            for (;;) {
-                ws(p);
-                if (object) { if (!str(p, t)) return false; ws(p); if (*p++ != ':') return false; }
-                if (!skip(p, depth + 1)) return false;
-                ws(p);
-                if (*p == ',') { ++p; continue; }
-                if (*p == close) { ++p; return true; }
-                return false;
-            }
-        }
-        const char* b = p;
-        while (*p && (std::isalnum(static_cast<unsigned char>(*p)) || *p == '-' || *p == '+' || *p == '.')) ++p;
-        return p != b;
-    }
-    explicit Config(const char* json) {
-        if (!json) return;
-        const char* p = json;
-        ws(p);
-        if (!*p) return;                                // "" = no configuration
-        if (*p != '{') { error = "the configuration is not a JSON object"; return; }
-        ++p; ws(p);
-        if (*p == '}') { ++p; ws(p); if (*p) error = "text after the configuration object"; return; }
-        for (;;) {
-            std::string key;
-            ws(p);
-            if (!str(p, key)) { error = "expected a key"; return; }
-            ws(p);
-            if (*p++ != ':') { error = "expected ':' after \"" + key + "\""; return; }
-            ws(p);
-            if (*p == '"') { std::string v; if (!str(p, v)) { error = "unterminated string for \"" + key + "\""; return; } strings[key] = v; }
-            else if (*p == '-' || std::isdigit(static_cast<unsigned char>(*p))) {
-                const char* q = p; long v;
-                if (integer(q, v)) { ints[key] = v; p = q; }
-                else { if (!skip(p)) { error = "bad number for \"" + key + "\""; return; } other.insert(key); }
-            } else if (*p == '[') {
-                const char* q = p + 1; std::vector<long> lst; bool ok = true;
-                ws(q);
-                if (*q == ']') ++q;
-                else for (;;) {
-                    long v; ws(q);
-                    if (!integer(q, v)) { ok = false; break; }
-                    lst.push_back(v); ws(q);
-                    if (*q == ',') { ++q; continue; }
-                    if (*q == ']') { ++q; break; }
-                    ok = false; break;
-                }
-                if (ok) { int_lists[key] = lst; p = q; }
-                else { if (!skip(p)) { error = "bad array for \"" + key + "\""; return; } other.insert(key); }
-            } else { if (!skip(p)) { error = "bad value for \"" + key + "\""; return; } other.insert(key); }
-            ws(p);
-            if (*p == ',') { ++p; continue; }
-            if (*p == '}') { ++p; break; }
-            error = "expected ',' or '}' after \"" + key + "\""; return;
-        }
-        ws(p);
-        if (*p) error = "text after the configuration object";
-    }
-    bool has(const std::string& k) const { return strings.count(k) || ints.count(k) || int_lists.count(k) || other.count(k); }
-    // typed reads: false (with `error` set) when the key is there with another type
-    bool get_int(const std::string& k, long dflt, long& out) {
-        out = dflt;
-        if (!has(k)) return true;
-        const auto it = ints.find(k);
-        if (it == ints.end()) { error = "\"" + k + "\" must be an integer"; return false; }
-        out = it->second;
-        return true;
-    }
-    bool get_string(const std::string& k, std::string& out, bool& present) {
-        present = false;
-        if (!has(k)) return true;
-        const auto it = strings.find(k);
-        if (it == strings.end()) { error = "\"" + k + "\" must be a string"; return false; }
-        out = it->second; present = true;
-        return true;
-    }
-    // an enumerated string: index into `allowed`, dflt when absent; false on any other value
-    bool get_choice(const std::string& k, std::initializer_list<const char*> allowed, int dflt, int& out) {
-        out = dflt;
-        std::string v; bool present;
-        if (!get_string(k, v, present)) return false;
-        if (!present) return true;
-        int i = 0;
-        for (const char* a : allowed) { if (v == a) { out = i; return true; } ++i; }
-        error = "\"" + k + "\": \"" + v + "\" is not one of";
-        for (const char* a : allowed) error += std::string(" \"") + a + "\"";
-        return false;
-    }
-};
 
 std::shared_ptr<Corpus> find_corpus(uint64_t id) {
     std::lock_guard<std::mutex> lk(g.corpora_mu);
@@ -506,18 +370,57 @@ std::shared_ptr<Corpus> find_corpus(uint64_t id) {
 
 #define NEED_INIT() std::shared_lock<std::shared_mutex> init_lk__(g.mu); do { if (!g.initialised) return YAMS_ERR_UNSUPPORTED; } while (0)
 
-// global row -> (shard, local row) under the stripe dealing
-inline uint32_t shard_of(uint64_t row, uint32_t n_sh) { return n_sh == 1 ? 0u : static_cast<uint32_t>((row / kStripeRows) % n_sh); }
-inline uint64_t local_of(uint64_t row, uint32_t n_sh) {
-    return n_sh == 1 ? row : (row / kStripeRows / n_sh) * kStripeRows + row % kStripeRows;
+// Which filter shadows a corpus of this dimension has: vs_corpus_append builds exactly these and view_of hands out exactly
+// these (a view naming a shadow that was never built would have the int8 tier's proof accept wrong rows in silence).
+inline bool has_bf16(uint32_t dim) { return g.want_bf16 && (dim & 3u) == 0; }
+inline bool has_i8(uint32_t dim) { return g.want_i8 && (dim & 63u) == 0 && dim >= 256; }
+
+// Shard i of a corpus as its engine sees it: rows, n_rows and dim, and of the rest what the search asks for.
+enum : unsigned { kViewTies = 1, kViewShadows = 2, kViewStripes = 4 };
+yams_scan_corpus_t view_of(const Corpus& c, uint32_t i, unsigned what) {
+    const ShardStore& s = c.sh[i];
+    yams_scan_corpus_t v;
+    std::memset(&v, 0, sizeof v);
+    v.rows = s.rows.as<float>(); v.n_rows = s.n_rows; v.dim = c.dim;
+    if ((what & kViewTies) && s.has_tie) { v.tie_rank = s.tie.as<uint32_t>(); v.rank_row = s.inv.as<uint32_t>(); }
+    if ((what & kViewShadows) && has_bf16(c.dim) && s.n_rows) { v.rows_bf16 = s.bf16.as<uint16_t>(); v.rows_nsq = s.nsq.as<float>(); }
+    if ((what & kViewShadows) && has_i8(c.dim) && s.n_rows) { v.rows_i8 = s.i8.as<int8_t>(); v.rows_i8_meta = s.i8meta.as<float>(); v.i8_flags = c.i8_flags > 0 ? static_cast<uint32_t>(c.i8_flags) : 0u; }
+    if ((what & kViewStripes) && c.sh.size() > 1) { v.stripe_rows = kStripeRows; v.n_stripes = static_cast<uint32_t>(c.sh.size()); v.stripe_index = i; }
+    return v;
 }
-// rows of a corpus of n rows that live on shard i
-inline uint64_t shard_rows(uint64_t n, uint32_t n_sh, uint32_t i) {
-    if (n_sh == 1) return n;
-    const uint64_t full = n / kStripeRows, rem = n % kStripeRows;
-    uint64_t r = (full / n_sh) * kStripeRows + ((full % n_sh) > i ? kStripeRows : 0);
-    if (full % n_sh == i) r += rem;
-    return r;
+
+// The malloc'd result of a search: hits[nq * max(k, 1)], every row preset to -1, and counts[max(nq, 1)], zeroed.  commit()
+// hands both to the caller (who frees them through the vtable's free function); what was not committed goes with the object.
+struct HitResult {
+    const size_t slots;
+    uint32_t* counts;
+    yams_scan_hit_t* hits;
+    HitResult(uint32_t nq, uint32_t k)
+        : slots(static_cast<size_t>(nq) * std::max<uint32_t>(k, 1)),
+          counts(static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)))),
+          hits(static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)))) {
+        for (size_t o = 0; hits && o < slots; ++o) hits[o].row = -1;
+    }
+    HitResult(const HitResult&) = delete;
+    ~HitResult() { std::free(counts); std::free(hits); }
+    bool ok() const { return counts && hits; }
+    yams_status_t commit(yams_scan_hit_t** out_hits, uint32_t** out_counts) {
+        *out_hits = hits; *out_counts = counts;
+        hits = nullptr; counts = nullptr;
+        return YAMS_OK;
+    }
+};
+
+// The host's allow-mask (document_hash / candidate_hashes restriction, :4137-4175; tombstones), dealt like the rows: shard i's
+// part goes into workspace `name` of the context (its device is current) and into the shard's view.
+yams_status_t attach_row_mask(yams_accel_ctx* x, const char* name, const uint32_t* row_mask_host, uint32_t n_sh, uint32_t i,
+                              yams_scan_corpus_t& v) {
+    const DealtMask m = deal_row_mask(row_mask_host, v.n_rows, kStripeRows, n_sh, i);
+    uint32_t* d_mask = nullptr;
+    YA_TRY(yams_accel::ws_get(x, name, m.words.size() * 4, (void**)&d_mask));
+    if (yams_accel_upload(x, d_mask, m.words.data(), m.words.size() * 4) != YAMS_OK) return YAMS_ERR_INTERNAL;
+    v.row_mask = d_mask; v.row_mask_count = m.bits;
+    return YAMS_OK;
 }
 
 // ---- vector_scan_v1 ---------------------------------------------------------------------------
@@ -573,15 +476,14 @@ yams_status_t vs_corpus_append(void*, uint64_t id, const float* rows, uint64_t n
     std::lock_guard<std::mutex> up(g.upload_mu);
     const uint32_t n_sh = static_cast<uint32_t>(c->sh.size());
     const uint64_t n0 = c->n_rows, n1 = n0 + n_rows;
-    if (shard_rows(n1, n_sh, 0) >= (1ull << 32)) return YAMS_ERR_UNSUPPORTED;
+    if (shard_rows(n1, kStripeRows, n_sh, 0) >= (1ull << 32)) return YAMS_ERR_UNSUPPORTED;
     const size_t rb = static_cast<size_t>(c->dim) * 4;
-    const bool bf16 = g.want_bf16 && (c->dim & 3u) == 0;
-    const bool i8 = g.want_i8 && (c->dim & 63u) == 0 && c->dim >= 256;
+    const bool bf16 = has_bf16(c->dim), i8 = has_i8(c->dim);
     size_t dev_total = 0, dev_free = 0;
     const auto t_begin = std::chrono::steady_clock::now();
     for (uint32_t i = 0; i < n_sh; ++i) {
         ShardStore& s = c->sh[i];
-        const uint64_t old = s.n_rows, now = shard_rows(n1, n_sh, i);
+        const uint64_t old = s.n_rows, now = shard_rows(n1, kStripeRows, n_sh, i);
         if (now == old) continue;
         (void)hipSetDevice(s.device);
         if (hipMemGetInfo(&dev_free, &dev_total) != hipSuccess || dev_total == 0) {
@@ -596,10 +498,10 @@ yams_status_t vs_corpus_append(void*, uint64_t id, const float* rows, uint64_t n
     // copy: runs of consecutive global rows inside one stripe are consecutive local rows
     for (uint64_t r = n0; r < n1;) {
         const uint64_t run = std::min<uint64_t>(n1 - r, n_sh == 1 ? n1 - r : kStripeRows - r % kStripeRows);
-        ShardStore& s = c->sh[shard_of(r, n_sh)];
-        yams_accel_ctx* uc = g.upload_ctx[shard_of(r, n_sh)];
+        ShardStore& s = c->sh[shard_of(r, kStripeRows, n_sh)];
+        yams_accel_ctx* uc = g.upload_ctx[shard_of(r, kStripeRows, n_sh)];
         (void)hipSetDevice(s.device);
-        if (!s.rows.h2d(local_of(r, n_sh) * rb, rows + (r - n0) * c->dim, run * rb, uc->stream)) return internal_error("append:4");
+        if (!s.rows.h2d(local_of(r, kStripeRows, n_sh) * rb, rows + (r - n0) * c->dim, run * rb, uc->stream)) return internal_error("append:4");
         r += run;
     }
     for (uint32_t i = 0; i < n_sh; ++i) if (yams_accel_ctx_synchronize(g.upload_ctx[i]) != YAMS_OK) return internal_error("append:4b");
@@ -616,7 +518,7 @@ yams_status_t vs_corpus_append(void*, uint64_t id, const float* rows, uint64_t n
             if (c->dim <= 4096) c->i8_flags = static_cast<int>(YAMS_SCAN_I8_ROTATED);   // (the rotated layout exists for 256 <= dim <= 4096)
         } else if (g.i8_layout == 0) {
             for (uint32_t i = 0; i < n_sh; ++i) {
-                const uint64_t now = shard_rows(n1, n_sh, i);
+                const uint64_t now = shard_rows(n1, kStripeRows, n_sh, i);
                 if (!now) continue;
                 uint32_t fl = 0;
                 (void)hipSetDevice(c->sh[i].device);
@@ -630,7 +532,7 @@ yams_status_t vs_corpus_append(void*, uint64_t id, const float* rows, uint64_t n
     }
     for (uint32_t i = 0; i < n_sh; ++i) {
         ShardStore& s = c->sh[i];
-        const uint64_t old = s.n_rows, now = shard_rows(n1, n_sh, i);
+        const uint64_t old = s.n_rows, now = shard_rows(n1, kStripeRows, n_sh, i);
         yams_accel_ctx* uc = g.upload_ctx[i];
         if (relayout && i8 && now) {     // every block of this shard again, in the layout the rows turned out to want
             if (yams_scan_build_shadow_i8_layout_device(uc, s.rows.as<float>(), 0, old, c->dim, static_cast<uint32_t>(c->i8_flags),
@@ -670,13 +572,7 @@ yams_status_t vs_corpus_set_tie_ranks(void*, uint64_t id, const uint32_t* ranks,
     if (!c) return YAMS_ERR_NOT_FOUND;
     std::unique_lock<std::shared_mutex> lk(c->mu);
     if (n_rows != c->n_rows || (!ranks && n_rows)) return YAMS_ERR_INVALID_ARG;
-    {
-        std::vector<uint8_t> seen(n_rows, 0);
-        for (uint64_t r = 0; r < n_rows; ++r) {
-            if (ranks[r] >= n_rows || seen[ranks[r]]) return YAMS_ERR_INVALID_ARG; // not a permutation
-            seen[ranks[r]] = 1;
-        }
-    }
+    if (!is_permutation_of_iota(ranks, n_rows)) return YAMS_ERR_INVALID_ARG;
     if (n_rows == 0) return YAMS_OK;
     std::lock_guard<std::mutex> up(g.upload_mu);
     const uint32_t n_sh = static_cast<uint32_t>(c->sh.size());
@@ -684,14 +580,8 @@ yams_status_t vs_corpus_set_tie_ranks(void*, uint64_t id, const uint32_t* ranks,
         ShardStore& s = c->sh[i];
         const uint64_t nl = s.n_rows;
         if (nl == 0) continue;
-        // local tie ranks: a permutation of 0..nl-1 that preserves the global order (the scan sorts ties
-        // by it inside the shard; the merge compares the global ranks through rank_of_row)
-        std::vector<uint32_t> glob(nl), order(nl), lrank(nl), linv(nl);
-        for (uint64_t l = 0; l < nl; ++l)
-            glob[l] = ranks[n_sh == 1 ? l : ((l / kStripeRows) * n_sh + i) * kStripeRows + l % kStripeRows];
-        std::iota(order.begin(), order.end(), 0u);
-        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return glob[x] < glob[y]; });
-        for (uint32_t p = 0; p < nl; ++p) { lrank[order[p]] = p; linv[p] = order[p]; }
+        std::vector<uint32_t> lrank, linv;
+        local_tie_ranks(ranks, nl, kStripeRows, n_sh, i, lrank, linv);
         if (!s.tie.ensure(nl * 4, s.rows.reserved / 16) || !s.inv.ensure(nl * 4, s.rows.reserved / 16)) return YAMS_ERR_RESOURCE_EXHAUSTED;
         (void)hipSetDevice(s.device);
         if (!s.tie.h2d(0, lrank.data(), nl * 4, g.upload_ctx[i]->stream) || !s.inv.h2d(0, linv.data(), nl * 4, g.upload_ctx[i]->stream) ||
@@ -778,33 +668,10 @@ yams_status_t vs_search_batch_ex(void*, uint64_t id, const float* queries, uint3
     const uint32_t n_sh = static_cast<uint32_t>(c->sh.size());
     std::vector<yams_scan_corpus_t> views(n_sh);
     for (uint32_t i = 0; i < n_sh; ++i) {
-        const ShardStore& s = c->sh[i];
-        yams_scan_corpus_t& v = views[i];
-        std::memset(&v, 0, sizeof v);
-        v.rows = s.rows.as<float>(); v.n_rows = s.n_rows; v.dim = c->dim;
-        if (s.has_tie) { v.tie_rank = s.tie.as<uint32_t>(); v.rank_row = s.inv.as<uint32_t>(); }
-        if (g.want_bf16 && (c->dim & 3u) == 0 && s.n_rows) { v.rows_bf16 = s.bf16.as<uint16_t>(); v.rows_nsq = s.nsq.as<float>(); }
-        if (g.want_i8 && (c->dim & 63u) == 0 && c->dim >= 256 && s.n_rows) { v.rows_i8 = s.i8.as<int8_t>(); v.rows_i8_meta = s.i8meta.as<float>(); v.i8_flags = c->i8_flags > 0 ? static_cast<uint32_t>(c->i8_flags) : 0u; }
-        if (n_sh > 1) { v.stripe_rows = kStripeRows; v.n_stripes = n_sh; v.stripe_index = i; }
-        if (row_mask_host && s.n_rows) { // document_hash / candidate_hashes restriction (:4137-4175), dealt like the rows
-            const size_t words = (s.n_rows + 31) / 32;
-            std::vector<uint32_t> local(words, 0u);
-            uint64_t bits = 0;
-            for (size_t w = 0; w < words; ++w) {
-                const uint64_t l0 = static_cast<uint64_t>(w) * 32;  // kStripeRows % 32 == 0: a local word is a global word
-                const uint64_t g0 = n_sh == 1 ? l0 : ((l0 / kStripeRows) * n_sh + i) * kStripeRows + l0 % kStripeRows;
-                uint32_t m = row_mask_host[g0 >> 5];
-                const uint64_t left = s.n_rows - l0;
-                if (left < 32) m &= (1u << left) - 1u;
-                local[w] = m;
-                bits += static_cast<uint64_t>(__builtin_popcount(m));
-            }
-            yams_accel_ctx* sc = yams_scan_sharded_lane_ctx(g.sharded, i, slot.lane);
-            (void)hipSetDevice(s.device);
-            uint32_t* d_mask = nullptr;
-            if (const yams_status_t ws = yams_accel::ws_get(sc, "plugin_row_mask", words * 4, (void**)&d_mask); ws != YAMS_OK) return ws;
-            if (yams_accel_upload(sc, d_mask, local.data(), words * 4) != YAMS_OK) return YAMS_ERR_INTERNAL;
-            v.row_mask = d_mask; v.row_mask_count = bits;
+        views[i] = view_of(*c, i, kViewTies | kViewShadows | kViewStripes);
+        if (row_mask_host && views[i].n_rows) {
+            (void)hipSetDevice(c->sh[i].device);
+            YA_TRY(attach_row_mask(yams_scan_sharded_lane_ctx(g.sharded, i, slot.lane), "plugin_row_mask", row_mask_host, n_sh, i, views[i]));
         }
     }
     // only semantic flags cross the vtable; filter selection stays with the library
@@ -813,29 +680,21 @@ yams_status_t vs_search_batch_ex(void*, uint64_t id, const float* queries, uint3
     // vec0's distance arithmetic: the call's own choice (any L2_ACC bit, or L2_ACC_EXPLICIT for a deliberate F64), else
     // the plugin's ("l2_accumulate" in the init config)
     if (metric == YAMS_SCAN_L2 && !(flags & (YAMS_SCAN_FLAG_L2_ACC_MASK | YAMS_SCAN_FLAG_L2_ACC_EXPLICIT))) prm.flags |= g.l2_acc;
-    const size_t slots = static_cast<size_t>(nq) * std::max<uint32_t>(k, 1);
-    std::vector<float> scores(slots), dist(slots);
-    std::vector<int64_t> rows(slots);
-    auto* counts = static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)));
-    auto* hits = static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)));
-    if (!counts || !hits) { std::free(counts); std::free(hits); return YAMS_ERR_INTERNAL; }
+    HitResult res(nq, k);
+    if (!res.ok()) return YAMS_ERR_INTERNAL;
+    std::vector<float> scores(res.slots), dist(res.slots);
+    std::vector<int64_t> rows(res.slots);
     yams_status_t s = yams_scan_sharded_submit(g.sharded, slot.lane, views.data(), queries, nq, &prm,
                                                c->has_ranks && n_sh > 1 ? c->rank_of_row.as<uint32_t>() : nullptr, 0,
                                                out_diag ? YAMS_SHARDED_SUBMIT_DIAG : 0u);
     if (s == YAMS_OK) {
         slot.held = false; // wait() frees the lane
-        s = yams_scan_sharded_wait(g.sharded, slot.lane, scores.data(), rows.data(), counts, dist.data(), out_diag);
+        s = yams_scan_sharded_wait(g.sharded, slot.lane, scores.data(), rows.data(), res.counts, dist.data(), out_diag);
     }
-    if (s != YAMS_OK) { std::free(counts); std::free(hits); return s; }
-    for (uint32_t q = 0; q < nq; ++q)
-        for (uint32_t i = 0; i < k; ++i) {
-            const size_t o = static_cast<size_t>(q) * k + i;
-            if (i < counts[q]) { hits[o].row = rows[o]; hits[o].similarity = scores[o]; hits[o].distance = dist[o]; }
-            else { hits[o].row = -1; hits[o].similarity = 0.f; hits[o].distance = 0.f; }
-        }
+    if (s != YAMS_OK) return s;
+    pack_hits(nq, k, res.counts, rows.data(), scores.data(), dist.data(), res.hits);
     ++g.searches;
-    *out_hits = hits; *out_counts = counts;
-    return YAMS_OK;
+    return res.commit(out_hits, out_counts);
 }
 
 yams_status_t vs_search_batch_masked(void* self, uint64_t id, const float* queries, uint32_t nq, uint32_t dim,
@@ -854,6 +713,64 @@ yams_status_t vs_search_batch(void* self, uint64_t id, const float* queries, uin
                                   out_counts, out_diag);
 }
 
+// ---- one scaffold for the three single-device engines (PQ, documents, entities) ---------------------------------------------
+// It owns the checks of a call (in this order: out-pointers, k, corpus, dimension, null inputs), the corpus's shared lock,
+// the refusal of a striped corpus, the result, the lease of a work context, the workspace "plugin_<engine>_*" for queries,
+// scores, rows, counts (and the matching-row counts), the query upload, the view with its allow-mask, the downloads and the
+// packing.  An engine gives: when there is nothing to find (beyond nq == 0), `reserve` for workspace of its own (taken
+// right after the queries'), and `run` for its side tables' uploads and its device call.
+struct SearchCall {
+    uint64_t id; const float* queries; bool inputs_given; uint32_t nq, dim, k; const uint32_t* row_mask_host;
+    yams_scan_hit_t** out_hits; uint32_t** out_counts; uint64_t* out_matching; yams_scan_diag_t* out_diag;
+};
+struct SearchSlots {
+    yams_accel_ctx* x; const yams_scan_corpus_t* view;
+    float* d_q; float* d_s; int64_t* d_r; uint32_t* d_n; uint64_t* d_m;
+};
+template <typename Empty, typename Reserve, typename Run>
+yams_status_t search_one_device(const SearchCall& a, const char* engine, unsigned view_what, bool matching, Empty&& nothing_to_find,
+                                Reserve&& reserve, Run&& run) {
+    NEED_INIT();
+    if (!a.out_hits || !a.out_counts) return YAMS_ERR_INVALID_ARG;
+    *a.out_hits = nullptr; *a.out_counts = nullptr;
+    if (a.k > YAMS_SCAN_MAX_K) return YAMS_ERR_UNSUPPORTED;
+    auto c = find_corpus(a.id);
+    if (!c) return YAMS_ERR_NOT_FOUND;
+    if (a.dim != c->dim) return YAMS_ERR_INVALID_ARG;           // (vector_database.cpp:545-550; entities: a row of another size lives in another corpus, :2858)
+    if (a.nq && !a.inputs_given) return YAMS_ERR_INVALID_ARG;
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    if (c->sh.size() != 1) return YAMS_ERR_UNSUPPORTED;
+    HitResult res(a.nq, a.k);
+    if (!res.ok()) return YAMS_ERR_INTERNAL;
+    if (a.nq == 0 || nothing_to_find(*c)) { if (a.out_diag) std::memset(a.out_diag, 0, sizeof *a.out_diag); return res.commit(a.out_hits, a.out_counts); }
+    (void)hipSetDevice(c->sh[0].device);
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    SearchSlots d{};
+    d.x = w.v;
+    const auto ws = [engine](const char* what) { return std::string("plugin_").append(engine).append("_").append(what); };
+    const size_t nq = a.nq;
+    YA_TRY(yams_accel::ws_get(d.x, ws("queries").c_str(), nq * a.dim * 4, (void**)&d.d_q));
+    YA_TRY(reserve(*c, d.x));
+    YA_TRY(yams_accel::ws_get(d.x, ws("scores").c_str(), res.slots * 4, (void**)&d.d_s));
+    YA_TRY(yams_accel::ws_get(d.x, ws("rows").c_str(), res.slots * 8, (void**)&d.d_r));
+    YA_TRY(yams_accel::ws_get(d.x, ws("counts").c_str(), nq * 4, (void**)&d.d_n));
+    if (matching) YA_TRY(yams_accel::ws_get(d.x, ws("matching").c_str(), nq * 8, (void**)&d.d_m));
+    if (yams_accel_upload(d.x, d.d_q, a.queries, nq * a.dim * 4) != YAMS_OK) return YAMS_ERR_INTERNAL;
+    yams_scan_corpus_t v = view_of(*c, 0, view_what);
+    if (a.row_mask_host && v.n_rows) YA_TRY(attach_row_mask(d.x, ws("mask").c_str(), a.row_mask_host, 1, 0, v));
+    d.view = &v;
+    YA_TRY(run(*c, d));
+    std::vector<float> scores(res.slots); std::vector<int64_t> rows(res.slots);
+    if (yams_accel_download(d.x, res.counts, d.d_n, nq * 4) != YAMS_OK ||
+        (a.k && yams_accel_download(d.x, scores.data(), d.d_s, res.slots * 4) != YAMS_OK) ||
+        (a.k && yams_accel_download(d.x, rows.data(), d.d_r, res.slots * 8) != YAMS_OK) ||
+        (a.out_matching && yams_accel_download(d.x, a.out_matching, d.d_m, nq * 8) != YAMS_OK)) return YAMS_ERR_INTERNAL;
+    pack_hits(a.nq, a.k, res.counts, rows.data(), scores.data(), nullptr, res.hits);
+    ++g.searches;
+    return res.commit(a.out_hits, a.out_counts);
+}
+const auto reserve_nothing = [](const Corpus&, yams_accel_ctx*) { return YAMS_OK; };
+
 // ---- version 2: the product-quantised engine over the mirror (yams_scan_pq_topk_device) ------------------------------------
 yams_status_t vs_pq_index_set(void*, uint64_t id, const uint8_t* codes, uint64_t n_codes, uint32_t m, const uint64_t* tie_keys,
                               const uint32_t* row_of_index) {
@@ -865,84 +782,43 @@ yams_status_t vs_pq_index_set(void*, uint64_t id, const uint8_t* codes, uint64_t
     c->pq.release();
     if (n_codes == 0) return YAMS_OK;
     if (!codes || m == 0 || m > 128 || n_codes >= (1ull << 32)) return YAMS_ERR_INVALID_ARG;
-    // rank of every tie-break key (ascending key, equal keys by index: the comparator of :3985-3990) and the mirror row
-    // behind every key index — once per index build, on the host
-    std::vector<uint32_t> order(n_codes), rank(n_codes), key_row(n_codes);
-    std::iota(order.begin(), order.end(), 0u);
-    if (tie_keys)
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return tie_keys[a] != tie_keys[b] ? tie_keys[a] < tie_keys[b] : a < b; });
-    for (uint64_t r = 0; r < n_codes; ++r) { rank[order[r]] = static_cast<uint32_t>(r); key_row[r] = row_of_index ? row_of_index[order[r]] : order[r]; }
-    PqIndex p; p.device = c->sh[0].device; p.n = n_codes; p.m = m;
-    (void)hipSetDevice(p.device);
+    std::vector<uint32_t> rank, key_row;      // once per index build, on the host
+    rank_pq_keys(tie_keys, row_of_index, n_codes, rank, key_row);
+    PqIndex p; p.n = n_codes; p.m = m;        // (goes with this scope, its arrays with it, unless it becomes the corpus's)
+    const int dev = c->sh[0].device;
+    (void)hipSetDevice(dev);
     Lease<yams_accel_ctx*> w(g.work_ctx);
     const size_t code_bytes = (static_cast<size_t>(n_codes) * m + 15) & ~static_cast<size_t>(15);
-    bool ok = yams_accel::ya_malloc(reinterpret_cast<void**>(&p.codes), code_bytes) == hipSuccess &&
-              yams_accel::ya_malloc(reinterpret_cast<void**>(&p.tie_rank), n_codes * 4) == hipSuccess &&
-              yams_accel::ya_malloc(reinterpret_cast<void**>(&p.key_row), n_codes * 4) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); p.release(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
-    ok = yams_accel_upload(w.v, p.codes, codes, static_cast<size_t>(n_codes) * m) == YAMS_OK &&
-         yams_accel_upload(w.v, p.tie_rank, rank.data(), n_codes * 4) == YAMS_OK &&
-         yams_accel_upload(w.v, p.key_row, key_row.data(), n_codes * 4) == YAMS_OK;
-    if (!ok) { p.release(); return YAMS_ERR_INTERNAL; }
-    c->pq = p;
+    if (!(p.codes.alloc(dev, code_bytes) && p.tie_rank.alloc(dev, n_codes * 4) && p.key_row.alloc(dev, n_codes * 4))) { (void)hipGetLastError(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    if (yams_accel_upload(w.v, p.codes, codes, static_cast<size_t>(n_codes) * m) != YAMS_OK ||
+        yams_accel_upload(w.v, p.tie_rank, rank.data(), n_codes * 4) != YAMS_OK ||
+        yams_accel_upload(w.v, p.key_row, key_row.data(), n_codes * 4) != YAMS_OK) return YAMS_ERR_INTERNAL;
+    c->pq = std::move(p);
     return YAMS_OK;
 }
 
 yams_status_t vs_search_pq(void*, uint64_t id, const float* queries, const float* luts, uint32_t nq, uint32_t dim, uint32_t k,
                            float threshold, uint32_t rerank_factor, uint32_t flags, const uint32_t* candidates, uint64_t n_candidates,
                            yams_scan_hit_t** out_hits, uint32_t** out_counts, yams_scan_diag_t* out_diag) {
-    NEED_INIT();
-    if (!out_hits || !out_counts) return YAMS_ERR_INVALID_ARG;
-    *out_hits = nullptr; *out_counts = nullptr;
-    if (k > YAMS_SCAN_MAX_K) return YAMS_ERR_UNSUPPORTED;
-    auto c = find_corpus(id);
-    if (!c) return YAMS_ERR_NOT_FOUND;
-    if (dim != c->dim) return YAMS_ERR_INVALID_ARG;
-    if (nq && (!queries || !luts)) return YAMS_ERR_INVALID_ARG;
     if (candidates == nullptr) n_candidates = 0;
-    std::shared_lock<std::shared_mutex> lk(c->mu);
-    if (c->sh.size() != 1) return YAMS_ERR_UNSUPPORTED;
-    const ShardStore& s = c->sh[0];
-    const PqIndex& p = c->pq;
-    const size_t slots = static_cast<size_t>(nq) * std::max<uint32_t>(k, 1);
-    auto* counts = static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)));
-    auto* hits = static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)));
-    if (!counts || !hits) { std::free(counts); std::free(hits); return YAMS_ERR_INTERNAL; }
-    auto done = [&](yams_status_t st) { if (st != YAMS_OK) { std::free(counts); std::free(hits); } else { *out_hits = hits; *out_counts = counts; } return st; };
-    for (size_t o = 0; o < slots; ++o) hits[o].row = -1;
-    // no index (or an empty one), no rows, k == 0, an empty candidate list: nothing (:3873-3880, :3946-3948)
-    if (nq == 0 || k == 0 || p.n == 0 || s.n_rows == 0 || (candidates && n_candidates == 0)) { if (out_diag) std::memset(out_diag, 0, sizeof *out_diag); return done(YAMS_OK); }
-    (void)hipSetDevice(s.device);
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    yams_accel_ctx* x = w.v;
-    float* d_q; float* d_l; uint32_t* d_c = nullptr; float* d_s; int64_t* d_r; uint32_t* d_n;
-    yams_status_t st;
-    if ((st = yams_accel::ws_get(x, "plugin_pq_queries", static_cast<size_t>(nq) * dim * 4, (void**)&d_q)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_pq_luts", static_cast<size_t>(nq) * p.m * 1024, (void**)&d_l)) != YAMS_OK) return done(st);
-    if (candidates && (st = yams_accel::ws_get(x, "plugin_pq_candidates", n_candidates * 4, (void**)&d_c)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_pq_scores", slots * 4, (void**)&d_s)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_pq_rows", slots * 8, (void**)&d_r)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_pq_counts", static_cast<size_t>(nq) * 4, (void**)&d_n)) != YAMS_OK) return done(st);
-    if (yams_accel_upload(x, d_q, queries, static_cast<size_t>(nq) * dim * 4) != YAMS_OK ||
-        yams_accel_upload(x, d_l, luts, static_cast<size_t>(nq) * p.m * 1024) != YAMS_OK ||
-        (candidates && yams_accel_upload(x, d_c, candidates, n_candidates * 4) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
-    yams_scan_corpus_t v;
-    std::memset(&v, 0, sizeof v);
-    v.rows = s.rows.as<float>(); v.n_rows = s.n_rows; v.dim = c->dim;
-    if (s.has_tie) { v.tie_rank = s.tie.as<uint32_t>(); v.rank_row = s.inv.as<uint32_t>(); }
-    yams_scan_pq_index_t pi{p.codes, p.n, p.m, 0, p.tie_rank, p.key_row};
-    yams_scan_pq_params_t prm{k, threshold, rerank_factor, flags & YAMS_PQ_SUM_MASK};
-    if ((st = yams_scan_pq_topk_device(x, &v, &pi, d_q, d_l, nq, &prm, d_c, n_candidates, d_s, d_r, d_n, out_diag)) != YAMS_OK) return done(st);
-    std::vector<float> scores(slots); std::vector<int64_t> rows(slots);
-    if (yams_accel_download(x, counts, d_n, static_cast<size_t>(nq) * 4) != YAMS_OK || yams_accel_download(x, scores.data(), d_s, slots * 4) != YAMS_OK ||
-        yams_accel_download(x, rows.data(), d_r, slots * 8) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
-    for (uint32_t q = 0; q < nq; ++q)
-        for (uint32_t i = 0; i < k && i < counts[q]; ++i) {
-            const size_t o = static_cast<size_t>(q) * k + i;
-            hits[o].row = rows[o]; hits[o].similarity = scores[o]; hits[o].distance = 1.0f - scores[o];
-        }
-    ++g.searches;
-    return done(YAMS_OK);
+    float* d_l = nullptr; uint32_t* d_c = nullptr;
+    const SearchCall a{id, queries, queries && luts, nq, dim, k, nullptr, out_hits, out_counts, nullptr, out_diag};
+    return search_one_device(a, "pq", kViewTies, false,
+        // no index (or an empty one), no rows, k == 0, an empty candidate list: nothing (:3873-3880, :3946-3948)
+        [&](const Corpus& c) { return k == 0 || c.pq.n == 0 || c.sh[0].n_rows == 0 || (candidates && n_candidates == 0); },
+        [&](const Corpus& c, yams_accel_ctx* x) -> yams_status_t {
+            YA_TRY(yams_accel::ws_get(x, "plugin_pq_luts", static_cast<size_t>(nq) * c.pq.m * 1024, (void**)&d_l));
+            if (candidates) YA_TRY(yams_accel::ws_get(x, "plugin_pq_candidates", n_candidates * 4, (void**)&d_c));
+            return YAMS_OK;
+        },
+        [&](const Corpus& c, const SearchSlots& d) -> yams_status_t {
+            const PqIndex& p = c.pq;
+            if (yams_accel_upload(d.x, d_l, luts, static_cast<size_t>(nq) * p.m * 1024) != YAMS_OK ||
+                (candidates && yams_accel_upload(d.x, d_c, candidates, n_candidates * 4) != YAMS_OK)) return YAMS_ERR_INTERNAL;
+            yams_scan_pq_index_t pi{p.codes, p.n, p.m, 0, p.tie_rank, p.key_row};
+            yams_scan_pq_params_t prm{k, threshold, rerank_factor, flags & YAMS_PQ_SUM_MASK};
+            return yams_scan_pq_topk_device(d.x, d.view, &pi, d.d_q, d_l, nq, &prm, d_c, n_candidates, d.d_s, d.d_r, d.d_n, out_diag);
+        });
 }
 
 void vs_free_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::free(hits); std::free(counts); }
@@ -971,24 +847,16 @@ yams_status_t ds_corpus_set_documents(void*, uint64_t id, const uint32_t* row_do
     if (n_rows != c->n_rows || (n_rows && !row_doc) || n_docs == YAMS_SCAN_NO_DOC) return YAMS_ERR_INVALID_ARG;
     for (uint64_t r = 0; r < n_rows; ++r)
         if (row_doc[r] != YAMS_SCAN_NO_DOC && row_doc[r] >= n_docs) return YAMS_ERR_INVALID_ARG;
-    if (doc_rank) {
-        std::vector<uint8_t> seen(n_docs, 0);
-        for (uint32_t d = 0; d < n_docs; ++d) {
-            if (doc_rank[d] >= n_docs || seen[doc_rank[d]]) return YAMS_ERR_INVALID_ARG; // not a permutation
-            seen[doc_rank[d]] = 1;
-        }
-    }
+    if (doc_rank && !is_permutation_of_iota(doc_rank, n_docs)) return YAMS_ERR_INVALID_ARG;
     c->docs.release();
-    DocMap m; m.device = c->sh[0].device; m.n_rows = n_rows; m.n_docs = n_docs;
+    DocMap m; m.n_rows = n_rows; m.n_docs = n_docs;      // (goes with this scope unless it becomes the corpus's)
     m.row_doc.assign(row_doc, row_doc + n_rows);
-    (void)hipSetDevice(m.device);
-    bool ok = (n_rows == 0 || yams_accel::ya_malloc(reinterpret_cast<void**>(&m.d_row_doc), n_rows * 4) == hipSuccess) &&
-              (!doc_rank || n_docs == 0 || yams_accel::ya_malloc(reinterpret_cast<void**>(&m.d_doc_rank), static_cast<size_t>(n_docs) * 4) == hipSuccess);
-    if (!ok) { (void)hipGetLastError(); m.release(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    const int dev = c->sh[0].device;
+    (void)hipSetDevice(dev);
+    if (!((n_rows == 0 || m.d_row_doc.alloc(dev, n_rows * 4)) && (!doc_rank || n_docs == 0 || m.d_doc_rank.alloc(dev, static_cast<size_t>(n_docs) * 4)))) { (void)hipGetLastError(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
     Lease<yams_accel_ctx*> w(g.work_ctx);
-    ok = (!m.d_row_doc || yams_accel_upload(w.v, m.d_row_doc, row_doc, n_rows * 4) == YAMS_OK) &&
-         (!m.d_doc_rank || yams_accel_upload(w.v, m.d_doc_rank, doc_rank, static_cast<size_t>(n_docs) * 4) == YAMS_OK);
-    if (!ok) { m.release(); return YAMS_ERR_INTERNAL; }
+    if ((m.d_row_doc && yams_accel_upload(w.v, m.d_row_doc, row_doc, n_rows * 4) != YAMS_OK) ||
+        (m.d_doc_rank && yams_accel_upload(w.v, m.d_doc_rank, doc_rank, static_cast<size_t>(n_docs) * 4) != YAMS_OK)) return YAMS_ERR_INTERNAL;
     c->docs = std::move(m);
     return YAMS_OK;
 }
@@ -996,75 +864,23 @@ yams_status_t ds_corpus_set_documents(void*, uint64_t id, const uint32_t* row_do
 yams_status_t ds_search_docs(void*, uint64_t id, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, float threshold,
                              const uint32_t* row_mask_host, yams_scan_hit_t** out_hits, uint32_t** out_counts,
                              uint64_t* out_matching, yams_scan_diag_t* out_diag) {
-    NEED_INIT();
-    if (!out_hits || !out_counts) return YAMS_ERR_INVALID_ARG;
-    *out_hits = nullptr; *out_counts = nullptr;
-    if (k > YAMS_SCAN_MAX_K) return YAMS_ERR_UNSUPPORTED;
-    auto c = find_corpus(id);
-    if (!c) return YAMS_ERR_NOT_FOUND;
-    if (dim != c->dim) return YAMS_ERR_INVALID_ARG;           // (vector_database.cpp:545-550)
-    if (nq && !queries) return YAMS_ERR_INVALID_ARG;
-    std::shared_lock<std::shared_mutex> lk(c->mu);
-    if (c->sh.size() != 1) return YAMS_ERR_UNSUPPORTED;
-    const ShardStore& s = c->sh[0];
-    const DocMap& dm = c->docs;
-    const size_t slots = static_cast<size_t>(nq) * std::max<uint32_t>(k, 1);
-    auto* counts = static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)));
-    auto* hits = static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)));
-    if (!counts || !hits) { std::free(counts); std::free(hits); return YAMS_ERR_INTERNAL; }
-    auto done = [&](yams_status_t st) { if (st != YAMS_OK) { std::free(counts); std::free(hits); } else { *out_hits = hits; *out_counts = counts; } return st; };
-    for (size_t o = 0; o < slots; ++o) hits[o].row = -1;
-    if (nq == 0) { if (out_diag) std::memset(out_diag, 0, sizeof *out_diag); return done(YAMS_OK); }
-    (void)hipSetDevice(s.device);
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    yams_accel_ctx* x = w.v;
-    float* d_q; float* d_s; int64_t* d_r; uint32_t* d_n; uint64_t* d_m;
-    yams_status_t st;
-    if ((st = yams_accel::ws_get(x, "plugin_doc_queries", static_cast<size_t>(nq) * dim * 4, (void**)&d_q)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_doc_scores", slots * 4, (void**)&d_s)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_doc_rows", slots * 8, (void**)&d_r)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_doc_counts", static_cast<size_t>(nq) * 4, (void**)&d_n)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_doc_matching", static_cast<size_t>(nq) * 8, (void**)&d_m)) != YAMS_OK) return done(st);
-    if (yams_accel_upload(x, d_q, queries, static_cast<size_t>(nq) * dim * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
-    yams_scan_corpus_t v;
-    std::memset(&v, 0, sizeof v);
-    v.rows = s.rows.as<float>(); v.n_rows = s.n_rows; v.dim = c->dim;
-    if (s.has_tie) { v.tie_rank = s.tie.as<uint32_t>(); v.rank_row = s.inv.as<uint32_t>(); }
-    if (row_mask_host && s.n_rows) {   // document_hash / candidate_hashes restriction (:4137-4175)
-        const size_t words = (s.n_rows + 31) / 32;
-        std::vector<uint32_t> mask(row_mask_host, row_mask_host + words);
-        if (s.n_rows % 32) mask.back() &= (1u << (s.n_rows % 32)) - 1u;
-        uint64_t bits = 0;
-        for (uint32_t m : mask) bits += static_cast<uint64_t>(__builtin_popcount(m));
-        uint32_t* d_mask;
-        if ((st = yams_accel::ws_get(x, "plugin_doc_mask", words * 4, (void**)&d_mask)) != YAMS_OK) return done(st);
-        if (yams_accel_upload(x, d_mask, mask.data(), words * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
-        v.row_mask = d_mask; v.row_mask_count = bits;
-    }
-    // the document map; rows appended after it was set have no document
-    yams_scan_docs_t docs{dm.d_row_doc, dm.d_doc_rank, dm.n_docs, 0};
-    if (s.n_rows > dm.n_rows) {
-        std::vector<uint32_t> padded(s.n_rows, YAMS_SCAN_NO_DOC);
-        std::copy(dm.row_doc.begin(), dm.row_doc.end(), padded.begin());
-        uint32_t* d_pad;
-        if ((st = yams_accel::ws_get(x, "plugin_doc_row_doc", padded.size() * 4, (void**)&d_pad)) != YAMS_OK) return done(st);
-        if (yams_accel_upload(x, d_pad, padded.data(), padded.size() * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
-        docs.row_doc = d_pad;
-    }
-    yams_scan_params_t prm{k, threshold, YAMS_SCAN_COSINE, 0};
-    if ((st = yams_scan_doc_topk_device(x, &v, &docs, d_q, nq, &prm, d_s, d_r, nullptr, d_n, d_m, out_diag)) != YAMS_OK) return done(st);
-    std::vector<float> scores(slots); std::vector<int64_t> rows(slots);
-    if (yams_accel_download(x, counts, d_n, static_cast<size_t>(nq) * 4) != YAMS_OK ||
-        (k && yams_accel_download(x, scores.data(), d_s, slots * 4) != YAMS_OK) ||
-        (k && yams_accel_download(x, rows.data(), d_r, slots * 8) != YAMS_OK) ||
-        (out_matching && yams_accel_download(x, out_matching, d_m, static_cast<size_t>(nq) * 8) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
-    for (uint32_t q = 0; q < nq; ++q)
-        for (uint32_t i = 0; i < k && i < counts[q]; ++i) {
-            const size_t o = static_cast<size_t>(q) * k + i;
-            hits[o].row = rows[o]; hits[o].similarity = scores[o]; hits[o].distance = 1.0f - scores[o];
-        }
-    ++g.searches;
-    return done(YAMS_OK);
+    const SearchCall a{id, queries, queries != nullptr, nq, dim, k, row_mask_host, out_hits, out_counts, out_matching, out_diag};
+    return search_one_device(a, "doc", kViewTies, true, [](const Corpus&) { return false; }, reserve_nothing,
+        [&](const Corpus& c, const SearchSlots& d) -> yams_status_t {
+            // the document map; rows appended after it was set have no document
+            const DocMap& dm = c.docs;
+            yams_scan_docs_t docs{dm.d_row_doc, dm.d_doc_rank, dm.n_docs, 0};
+            if (d.view->n_rows > dm.n_rows) {
+                std::vector<uint32_t> padded(d.view->n_rows, YAMS_SCAN_NO_DOC);
+                std::copy(dm.row_doc.begin(), dm.row_doc.end(), padded.begin());
+                uint32_t* d_pad;
+                YA_TRY(yams_accel::ws_get(d.x, "plugin_doc_row_doc", padded.size() * 4, (void**)&d_pad));
+                if (yams_accel_upload(d.x, d_pad, padded.data(), padded.size() * 4) != YAMS_OK) return YAMS_ERR_INTERNAL;
+                docs.row_doc = d_pad;
+            }
+            yams_scan_params_t prm{k, threshold, YAMS_SCAN_COSINE, 0};
+            return yams_scan_doc_topk_device(d.x, d.view, &docs, d.d_q, nq, &prm, d.d_s, d.d_r, nullptr, d.d_n, d.d_m, out_diag);
+        });
 }
 
 void ds_free_doc_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::free(hits); std::free(counts); }
@@ -1089,20 +905,19 @@ yams_status_t es_corpus_set_attributes(void*, uint64_t id, uint64_t first_row, u
     if (types) std::copy(types, types + n_rows, e.type.begin() + first_row);
     if (node_types) std::copy(node_types, node_types + n_rows, e.node.begin() + first_row);
     if (docs) std::copy(docs, docs + n_rows, e.doc.begin() + first_row);
-    e.release_device();
-    e.n_rows = 0; e.device = c->sh[0].device;
+    e.d_type = {}; e.d_node = {}; e.d_doc = {};               // (the old columns go first: the new ones may need their memory)
+    e.n_rows = 0;
     if (c->n_rows == 0) return YAMS_OK;
-    (void)hipSetDevice(e.device);
+    const int dev = c->sh[0].device;
+    (void)hipSetDevice(dev);
     const size_t n = c->n_rows;
-    if (yams_accel::ya_malloc(reinterpret_cast<void**>(&e.d_type), n) != hipSuccess ||
-        yams_accel::ya_malloc(reinterpret_cast<void**>(&e.d_node), n * 4) != hipSuccess ||
-        yams_accel::ya_malloc(reinterpret_cast<void**>(&e.d_doc), n * 4) != hipSuccess) {
-        (void)hipGetLastError(); e.release_device();          // (the host copies stay: the next search pads from them)
-        return YAMS_ERR_RESOURCE_EXHAUSTED;
-    }
+    DevArray<uint8_t> t; DevArray<uint32_t> nd, dc;            // (go with this scope unless they become the corpus's; the host copies
+                                                               //  stay either way: the next search pads from them)
+    if (!(t.alloc(dev, n) && nd.alloc(dev, n * 4) && dc.alloc(dev, n * 4))) { (void)hipGetLastError(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
     Lease<yams_accel_ctx*> w(g.work_ctx);
-    if (yams_accel_upload(w.v, e.d_type, e.type.data(), n) != YAMS_OK || yams_accel_upload(w.v, e.d_node, e.node.data(), n * 4) != YAMS_OK ||
-        yams_accel_upload(w.v, e.d_doc, e.doc.data(), n * 4) != YAMS_OK) { e.release_device(); return YAMS_ERR_INTERNAL; }
+    if (yams_accel_upload(w.v, t, e.type.data(), n) != YAMS_OK || yams_accel_upload(w.v, nd, e.node.data(), n * 4) != YAMS_OK ||
+        yams_accel_upload(w.v, dc, e.doc.data(), n * 4) != YAMS_OK) return YAMS_ERR_INTERNAL;
+    e.d_type = std::move(t); e.d_node = std::move(nd); e.d_doc = std::move(dc);
     e.n_rows = n;
     return YAMS_OK;
 }
@@ -1110,77 +925,26 @@ yams_status_t es_corpus_set_attributes(void*, uint64_t id, uint64_t first_row, u
 yams_status_t es_search_entities(void*, uint64_t id, const float* queries, const yams_scan_entity_filter_t* filters, uint32_t nq,
                                  uint32_t dim, uint32_t k, float threshold, const uint32_t* row_mask_host, yams_scan_hit_t** out_hits,
                                  uint32_t** out_counts, uint64_t* out_matching, yams_scan_diag_t* out_diag) {
-    NEED_INIT();
-    if (!out_hits || !out_counts) return YAMS_ERR_INVALID_ARG;
-    *out_hits = nullptr; *out_counts = nullptr;
-    if (k > YAMS_SCAN_MAX_K) return YAMS_ERR_UNSUPPORTED;
-    auto c = find_corpus(id);
-    if (!c) return YAMS_ERR_NOT_FOUND;
-    if (dim != c->dim) return YAMS_ERR_INVALID_ARG;           // (a row of another size is skipped, :2858: such rows live in another corpus)
-    if (nq && !queries) return YAMS_ERR_INVALID_ARG;
-    std::shared_lock<std::shared_mutex> lk(c->mu);
-    if (c->sh.size() != 1) return YAMS_ERR_UNSUPPORTED;
-    const ShardStore& s = c->sh[0];
-    const EntityCols& e = c->ents;
-    const size_t slots = static_cast<size_t>(nq) * std::max<uint32_t>(k, 1);
-    auto* counts = static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)));
-    auto* hits = static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)));
-    if (!counts || !hits) { std::free(counts); std::free(hits); return YAMS_ERR_INTERNAL; }
-    auto done = [&](yams_status_t st) { if (st != YAMS_OK) { std::free(counts); std::free(hits); } else { *out_hits = hits; *out_counts = counts; } return st; };
-    for (size_t o = 0; o < slots; ++o) hits[o].row = -1;
-    if (nq == 0) { if (out_diag) std::memset(out_diag, 0, sizeof *out_diag); return done(YAMS_OK); }
-    (void)hipSetDevice(s.device);
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    yams_accel_ctx* x = w.v;
-    float* d_q; float* d_s; int64_t* d_r; uint32_t* d_n; uint64_t* d_m;
-    yams_status_t st;
-    if ((st = yams_accel::ws_get(x, "plugin_ent_queries", static_cast<size_t>(nq) * dim * 4, (void**)&d_q)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_ent_scores", slots * 4, (void**)&d_s)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_ent_rows", slots * 8, (void**)&d_r)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_ent_counts", static_cast<size_t>(nq) * 4, (void**)&d_n)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_ent_matching", static_cast<size_t>(nq) * 8, (void**)&d_m)) != YAMS_OK) return done(st);
-    if (yams_accel_upload(x, d_q, queries, static_cast<size_t>(nq) * dim * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
-    yams_scan_corpus_t v;
-    std::memset(&v, 0, sizeof v);
-    v.rows = s.rows.as<float>(); v.n_rows = s.n_rows; v.dim = c->dim;
-    if (row_mask_host && s.n_rows) {   // tombstones / host-side restrictions
-        const size_t words = (s.n_rows + 31) / 32;
-        std::vector<uint32_t> mask(row_mask_host, row_mask_host + words);
-        if (s.n_rows % 32) mask.back() &= (1u << (s.n_rows % 32)) - 1u;
-        uint64_t bits = 0;
-        for (uint32_t m : mask) bits += static_cast<uint64_t>(__builtin_popcount(m));
-        uint32_t* d_mask;
-        if ((st = yams_accel::ws_get(x, "plugin_ent_mask", words * 4, (void**)&d_mask)) != YAMS_OK) return done(st);
-        if (yams_accel_upload(x, d_mask, mask.data(), words * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
-        v.row_mask = d_mask; v.row_mask_count = bits;
-    }
-    // the attribute columns; rows appended after they were last set carry the "unset" values
-    yams_scan_entities_t cols{e.d_type, e.d_node, e.d_doc};
-    if (s.n_rows > e.n_rows) {
-        const size_t n = s.n_rows;
-        std::vector<uint8_t> t(n, YAMS_SCAN_ENTITY_TYPE_UNSET); std::vector<uint32_t> nd(n, YAMS_SCAN_ENTITY_UNSET), dc(n, YAMS_SCAN_ENTITY_UNSET);
-        std::copy(e.type.begin(), e.type.end(), t.begin()); std::copy(e.node.begin(), e.node.end(), nd.begin());
-        std::copy(e.doc.begin(), e.doc.end(), dc.begin());
-        uint8_t* p;
-        const size_t off = (n + 15) & ~static_cast<size_t>(15);
-        if ((st = yams_accel::ws_get(x, "plugin_ent_cols", off + n * 8, (void**)&p)) != YAMS_OK) return done(st);
-        if (yams_accel_upload(x, p, t.data(), n) != YAMS_OK || yams_accel_upload(x, p + off, nd.data(), n * 4) != YAMS_OK ||
-            yams_accel_upload(x, p + off + n * 4, dc.data(), n * 4) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
-        cols = yams_scan_entities_t{p, reinterpret_cast<uint32_t*>(p + off), reinterpret_cast<uint32_t*>(p + off + n * 4)};
-    }
-    if ((st = yams_scan_entity_topk_device(x, &v, &cols, d_q, filters, nq, k, threshold, d_s, d_r, d_n, d_m, out_diag)) != YAMS_OK) return done(st);
-    std::vector<float> scores(slots); std::vector<int64_t> rows(slots);
-    if (yams_accel_download(x, counts, d_n, static_cast<size_t>(nq) * 4) != YAMS_OK ||
-        (k && yams_accel_download(x, scores.data(), d_s, slots * 4) != YAMS_OK) ||
-        (k && yams_accel_download(x, rows.data(), d_r, slots * 8) != YAMS_OK) ||
-        (out_matching && yams_accel_download(x, out_matching, d_m, static_cast<size_t>(nq) * 8) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
-    for (uint32_t q = 0; q < nq; ++q)
-        for (uint32_t i = 0; i < k && i < counts[q]; ++i) {
-            const size_t o = static_cast<size_t>(q) * k + i;
-            hits[o].row = rows[o]; hits[o].similarity = scores[o]; hits[o].distance = 1.0f - scores[o];
-        }
-    ++g.searches;
-    return done(YAMS_OK);
+    const SearchCall a{id, queries, queries != nullptr, nq, dim, k, row_mask_host, out_hits, out_counts, out_matching, out_diag};
+    return search_one_device(a, "ent", 0, true, [](const Corpus&) { return false; }, reserve_nothing,
+        [&](const Corpus& c, const SearchSlots& d) -> yams_status_t {
+            // the attribute columns; rows appended after they were last set carry the "unset" values
+            const EntityCols& e = c.ents;
+            yams_scan_entities_t cols{e.d_type, e.d_node, e.d_doc};
+            if (d.view->n_rows > e.n_rows) {
+                const size_t n = d.view->n_rows;
+                std::vector<uint8_t> t(n, YAMS_SCAN_ENTITY_TYPE_UNSET); std::vector<uint32_t> nd(n, YAMS_SCAN_ENTITY_UNSET), dc(n, YAMS_SCAN_ENTITY_UNSET);
+                std::copy(e.type.begin(), e.type.end(), t.begin()); std::copy(e.node.begin(), e.node.end(), nd.begin());
+                std::copy(e.doc.begin(), e.doc.end(), dc.begin());
+                uint8_t* p;
+                const size_t off = (n + 15) & ~static_cast<size_t>(15);
+                YA_TRY(yams_accel::ws_get(d.x, "plugin_ent_cols", off + n * 8, (void**)&p));
+                if (yams_accel_upload(d.x, p, t.data(), n) != YAMS_OK || yams_accel_upload(d.x, p + off, nd.data(), n * 4) != YAMS_OK ||
+                    yams_accel_upload(d.x, p + off + n * 4, dc.data(), n * 4) != YAMS_OK) return YAMS_ERR_INTERNAL;
+                cols = yams_scan_entities_t{p, reinterpret_cast<uint32_t*>(p + off), reinterpret_cast<uint32_t*>(p + off + n * 4)};
+            }
+            return yams_scan_entity_topk_device(d.x, d.view, &cols, d.d_q, filters, nq, k, threshold, d.d_s, d.d_r, d.d_n, d.d_m, out_diag);
+        });
 }
 
 void es_free_entity_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::free(hits); std::free(counts); }
@@ -1296,11 +1060,6 @@ yams_semantic_graph_v1 g_semantic_graph = {YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION,
 // and searches of different host threads overlap on the device instead of queueing on one mutex.
 // One SHA-256 chain is sequential: ~35 MB/s on a device lane, > 1 GB/s on a host core.  Work the device is worse
 // at is refused (YAMS_ERR_UNSUPPORTED: the host hashes it itself), not served slowly — see the header.
-bool chains_suit_the_device(const size_t* lens, size_t n) {
-    size_t longest = 0, total = 0;
-    for (size_t i = 0; i < n; ++i) { longest = std::max(longest, lens[i]); total += lens[i]; }
-    return longest <= std::max<size_t>(YAMS_HASH_LONE_CHAIN_MAX, total / YAMS_HASH_CHAIN_RATIO);
-}
 yams_status_t ch_hash(void*, const uint8_t* data, size_t n, char out_hex[65]) {
     NEED_INIT();
     if (n > YAMS_HASH_LONE_CHAIN_MAX) { ++g.refused_chains; return YAMS_ERR_UNSUPPORTED; }
@@ -1414,13 +1173,9 @@ yams_status_t ch_stream_finalize(void*, void* s, char out_hex[65]) {
     for (int i = 7; i >= 0; --i) hs->pending.push_back(static_cast<uint8_t>(bits >> (8 * i)));
     const yams_status_t st = flush_whole_blocks(hs);
     if (st != YAMS_OK) return st;
-    static const char kHex[] = "0123456789abcdef";
-    for (int i = 0; i < 8; ++i)
-        for (int b = 0; b < 4; ++b) {
-            const uint8_t v = static_cast<uint8_t>(hs->state[i] >> (24 - 8 * b));
-            out_hex[8 * i + 2 * b] = kHex[v >> 4]; out_hex[8 * i + 2 * b + 1] = kHex[v & 15];
-        }
-    out_hex[64] = 0;
+    uint8_t digest[32];            // the state's words, big-endian
+    for (int i = 0; i < 32; ++i) digest[i] = static_cast<uint8_t>(hs->state[i / 4] >> (24 - 8 * (i % 4)));
+    to_hex(digest, out_hex);
     // "Reset for potential reuse" (sha256_hasher.cpp:103-106)
     std::memcpy(hs->state, kShaInit, 32);
     hs->pending.clear(); hs->total = 0;
@@ -1428,24 +1183,6 @@ yams_status_t ch_stream_finalize(void*, void* s, char out_hex[65]) {
     return YAMS_OK;
 }
 void ch_stream_destroy(void*, void* s) { delete static_cast<HashStream*>(s); }
-
-// hex (either case) -> 32 raw bytes; false on anything that is not 64 hex digits
-bool parse_hex32(const char* hex, uint8_t out[32]) {
-    for (int i = 0; i < 32; ++i) {
-        int v = 0;
-        for (int j = 0; j < 2; ++j) {
-            const char c = hex[2 * i + j];
-            int d;
-            if (c >= '0' && c <= '9') d = c - '0';
-            else if (c >= 'a' && c <= 'f') d = c - 'a' + 10;
-            else if (c >= 'A' && c <= 'F') d = c - 'A' + 10;
-            else return false;
-            v = v * 16 + d;
-        }
-        out[i] = static_cast<uint8_t>(v);
-    }
-    return hex[64] == 0;
-}
 
 yams_status_t ch_verify_many(void*, const uint8_t* const* msgs, const size_t* lens, const char* expected_hex,
                              size_t n, uint8_t* out_valid) {
@@ -1583,11 +1320,6 @@ yams_status_t ck_chunk_data(void* self, const uint8_t* data, size_t n, const yam
 }
 void ck_free_chunks(void*, yams_chunk_ref_t* chunks, size_t) { std::free(chunks); }
 
-void to_hex(const uint8_t* d, char out[65]) {
-    static const char kHexDigits[] = "0123456789abcdef";
-    for (int i = 0; i < 32; ++i) { out[2 * i] = kHexDigits[d[i] >> 4]; out[2 * i + 1] = kHexDigits[d[i] & 15]; }
-    out[64] = 0;
-}
 void ck_free_chunk_batch(void*, yams_chunk_batch_t* b) {
     if (!b) return;
     std::free(b->first_chunk); std::free(b->chunks); std::free(b->buffer_hash_hex); std::free(b);
@@ -1784,34 +1516,21 @@ void yams_plugin_shutdown(void) {
 int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out_iface) {
     if (!iface_id || !out_iface) return YAMS_PLUGIN_ERR_INVALID;
     *out_iface = nullptr;
-    if (std::strcmp(iface_id, YAMS_IFACE_VECTOR_SCAN_V1) == 0) {
-        if (version < 1 || version > YAMS_IFACE_VECTOR_SCAN_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
-        *out_iface = &g_vector_scan; return YAMS_PLUGIN_OK;
-    }
-    if (std::strcmp(iface_id, YAMS_IFACE_VECTOR_DOC_SCAN_V1) == 0) { // (not in the manifest: see the header)
-        if (version < 1 || version > YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
-        *out_iface = &g_vector_doc_scan; return YAMS_PLUGIN_OK;
-    }
-    if (std::strcmp(iface_id, YAMS_IFACE_VECTOR_ENTITY_SCAN_V1) == 0) { // (not in the manifest: see the header)
-        if (version < 1 || version > YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
-        *out_iface = &g_vector_entity_scan; return YAMS_PLUGIN_OK;
-    }
-    if (std::strcmp(iface_id, YAMS_IFACE_TOPOLOGY_CLUSTER_V1) == 0) { // (not in the manifest: see the header)
-        if (version < 1 || version > YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
-        *out_iface = &g_topology_cluster; return YAMS_PLUGIN_OK;
-    }
-    if (std::strcmp(iface_id, YAMS_IFACE_SEMANTIC_GRAPH_V1) == 0) { // (not in the manifest: see the header)
-        if (version < 1 || version > YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
-        *out_iface = &g_semantic_graph; return YAMS_PLUGIN_OK;
-    }
-    if (std::strcmp(iface_id, YAMS_IFACE_CONTENT_HASH_V1) == 0) {
-        if (version < 1 || version > YAMS_IFACE_CONTENT_HASH_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
-        *out_iface = &g_content_hash; return YAMS_PLUGIN_OK;
-    }
-    if (std::strcmp(iface_id, YAMS_IFACE_CHUNKER_V1) == 0) {
-        if (version < 1 || version > YAMS_IFACE_CHUNKER_V1_VERSION) return YAMS_PLUGIN_ERR_NOT_FOUND;
-        *out_iface = &g_chunker; return YAMS_PLUGIN_OK;
-    }
+    // (only vector_scan_v1, content_hash_v1 and chunker_v1 are in the manifest: see the header)
+    const struct { const char* id; uint32_t max_version; void* vtable; } kInterfaces[] = {
+        {YAMS_IFACE_VECTOR_SCAN_V1, YAMS_IFACE_VECTOR_SCAN_V1_VERSION, &g_vector_scan},
+        {YAMS_IFACE_VECTOR_DOC_SCAN_V1, YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION, &g_vector_doc_scan},
+        {YAMS_IFACE_VECTOR_ENTITY_SCAN_V1, YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION, &g_vector_entity_scan},
+        {YAMS_IFACE_TOPOLOGY_CLUSTER_V1, YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION, &g_topology_cluster},
+        {YAMS_IFACE_SEMANTIC_GRAPH_V1, YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION, &g_semantic_graph},
+        {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
+        {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};
+    for (const auto& f : kInterfaces)
+        if (std::strcmp(iface_id, f.id) == 0) {
+            if (version < 1 || version > f.max_version) return YAMS_PLUGIN_ERR_NOT_FOUND;
+            *out_iface = f.vtable;
+            return YAMS_PLUGIN_OK;
+        }
     return YAMS_PLUGIN_ERR_NOT_FOUND;
 }
 
