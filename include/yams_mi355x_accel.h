@@ -1022,6 +1022,59 @@ YAMS_ACCEL_API yams_status_t yams_dedup_insert_host(yams_dedup_set* set, const u
 YAMS_ACCEL_API yams_status_t yams_dedup_probe_host(yams_dedup_set* set, const uint8_t* digests_host,
                                                    uint64_t n, uint8_t* out_exists_host);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batched CRC-32: CompressedStorageEngine's header.uncompressedCRC32
+ * (src/storage/compressed_storage_engine.cpp:49-59, 524) and the read side's check of it (:594-627,
+ * src/storage/storage_engine.cpp:102-120, src/compression/compression_utils.cpp:31-52,
+ * src/compression/integrity_validator.cpp:36-65).  The standard CRC-32: reflected polynomial 0xEDB88320,
+ * initial value ~0, final xor ~0, check value 0xCBF43926; the CRC of an empty message is 0.
+ *
+ * CRC is linear over GF(2), so a message is cut into segments of YAMS_CRC32_SEGMENT_BYTES that are computed
+ * independently and folded: one long message spreads over the device like many short ones.  Messages start at any
+ * byte offset and have any length up to 2^40; only the 16-byte-aligned granules that hold message bytes are read.
+ * Every call returns with its results complete (it reads one word back to size its workspace of
+ * O(total bytes / segment + n) bytes).  n == 0: YAMS_OK, nothing written; NULL ctx or tables: YAMS_ERR_INVALID_ARG;
+ * 2^31 messages or more: YAMS_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------- */
+#define YAMS_CRC32_SEGMENT_BYTES 4096u
+/* Pure, needs no device: the CRC-32 of A || B from crc(A), crc(B) and |B| (updateCRC32,
+ * compression_utils.cpp:42-52, by linearity). */
+YAMS_ACCEL_API uint32_t yams_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* Message i = data[offsets[i] .. offsets[i] + lengths[i]); offsets / lengths: DEVICE arrays; out_crc32: DEVICE u32[n_msgs],
+ * in input order.  Messages may overlap. */
+YAMS_ACCEL_API yams_status_t yams_crc32_batch_device(yams_accel_ctx* ctx, const uint8_t* data,
+                                                     const uint64_t* offsets, const uint64_t* lengths,
+                                                     uint64_t n_msgs, uint32_t* out_crc32);
+/* The chunks of an ingest result (chunk_blob / chunk_offset / chunk_size of yams_ingest_device or yams_cdc_chunk_device
+ * over the same `data` and blob_offsets_host) while the bytes are still resident.  select: device u8[n_chunks] or NULL —
+ * e.g. out_is_new of yams_dedup_insert_device: only new chunks are stored; an unselected chunk's bytes are not read and
+ * its entry is 0.  out_crc32: DEVICE u32[n_chunks].  The result's arrays are only read. */
+YAMS_ACCEL_API yams_status_t yams_crc32_chunks_device(yams_accel_ctx* ctx, const uint8_t* data,
+                                                      const uint64_t* blob_offsets_host, uint64_t n_blobs,
+                                                      const yams_ingest_result_t* chunks, const uint8_t* select,
+                                                      uint32_t* out_crc32);
+/* The read side (storage_engine.cpp:102-120, compressed_storage_engine.cpp:594-627): out_valid[i] =
+ * (crc(message i) == expected_crc32[i]); expected_crc32 / out_valid: DEVICE arrays; *out_n_invalid (host, nullable)
+ * counts the mismatches. */
+YAMS_ACCEL_API yams_status_t yams_crc32_verify_device(yams_accel_ctx* ctx, const uint8_t* data,
+                                                      const uint64_t* offsets, const uint64_t* lengths, uint64_t n,
+                                                      const uint32_t* expected_crc32, uint8_t* out_valid,
+                                                      uint64_t* out_n_invalid);
+/* Messages in HOST memory: one upload, one batch, one download.  A NULL message needs length 0. */
+YAMS_ACCEL_API yams_status_t yams_crc32_many_host(yams_accel_ctx* ctx, const uint8_t* const* msgs_host,
+                                                  const size_t* lens, size_t n_msgs, uint32_t* out_crc32_host);
+/* yams_ingest_host plus the CRC-32 of every chunk: out_chunk_crc32 [chunk_cap] (required unless chunk_cap is 0), filled
+ * like out_chunk_offset.  The same implementation with one more pass and one more copy per batch, on the one upload;
+ * every other output is what yams_ingest_host gives for the same arguments. */
+YAMS_ACCEL_API yams_status_t yams_ingest_host_crc32(yams_accel_ctx* ctx, const uint8_t* const* blobs_host,
+                                                    const uint64_t* blob_lengths, uint64_t n_blobs,
+                                                    const yams_cdc_config_t* cfg, uint32_t flags,
+                                                    uint64_t batch_bytes, uint64_t* out_blob_first,
+                                                    uint64_t* out_chunk_offset, uint64_t* out_chunk_size,
+                                                    uint8_t* out_chunk_digest, uint64_t chunk_cap,
+                                                    uint8_t* out_blob_digest, uint64_t* out_n_chunks,
+                                                    uint32_t* out_chunk_crc32);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Plugin vtables (obtained through yams_plugin_get_interface)                                  */
 /* ------------------------------------------------------------------------------------------ */
@@ -1254,6 +1307,25 @@ typedef struct yams_content_hash_v1 {
     yams_status_t (*dedup_size)(void* self, uint64_t set_id, uint64_t* out_entries);
     yams_status_t (*dedup_destroy)(void* self, uint64_t set_id);
 } yams_content_hash_v1;
+
+/* The compressed store's checksum (yams_crc32_many_host) for a host that holds the bytes in its own memory:
+ * calculateCRC32 / updateCRC32 of include/yams/compression/compression_utils.h:16, 24 and the batched forms a device
+ * needs to be worthwhile.  A separate interface, version 1, served by yams_plugin_get_interface and NOT listed in the
+ * manifest, for the reason given at vector_doc_scan_v1.  Without a device every call returns YAMS_ERR_UNSUPPORTED.
+ * crc32_many through this door is a second PCIe crossing of bytes chunk_many already saw; the flat ABI offers the
+ * fused form (yams_crc32_chunks_device after yams_ingest_device). */
+#define YAMS_IFACE_CONTENT_CHECKSUM_V1 "content_checksum_v1"
+#define YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION 1u
+typedef struct yams_content_checksum_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION */
+    void* self;
+    yams_status_t (*crc32)(void* self, const uint8_t* data, size_t n, uint32_t* out);
+    yams_status_t (*crc32_many)(void* self, const uint8_t* const* msgs, const size_t* lens, size_t n_msgs,
+                                uint32_t* out /* [n_msgs] */);
+    /* out_valid[i] = 1 iff CRC-32(msgs[i]) == expected[i] */
+    yams_status_t (*verify_many)(void* self, const uint8_t* const* msgs, const size_t* lens,
+                                 const uint32_t* expected /* [n_msgs] */, size_t n_msgs, uint8_t* out_valid);
+} yams_content_checksum_v1;
 
 typedef struct yams_chunk_ref_s { /* ChunkRef, chunker.h:32-41 (hash as hex) */
     uint64_t offset;

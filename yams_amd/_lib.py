@@ -246,6 +246,18 @@ class ContentHashV1(C.Structure):
     ]
 
 
+class ContentChecksumV1(C.Structure):  # content_checksum_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("crc32", C.CFUNCTYPE(ST, vp, u8p, C.c_size_t, u32p)),
+        ("crc32_many", C.CFUNCTYPE(ST, vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, u32p)),
+        ("verify_many", C.CFUNCTYPE(ST, vp, C.POINTER(vp), C.POINTER(C.c_size_t), u32p, C.c_size_t, u8p)),
+    ]
+
+
+CRC32_SEGMENT_BYTES = 4096           # YAMS_CRC32_SEGMENT_BYTES
+
+
 class ChunkBatch(C.Structure):
     _fields_ = [("n_buffers", C.c_size_t), ("n_chunks", C.c_size_t), ("first_chunk", C.POINTER(C.c_size_t)),
                 ("chunks", C.POINTER(ChunkRef)), ("buffer_hash_hex", C.POINTER(C.c_char))]
@@ -294,6 +306,7 @@ EXPORTS = [
     "yams_dedup_set_create", "yams_dedup_set_destroy", "yams_dedup_set_size", "yams_dedup_insert_device",
     "yams_dedup_probe_device", "yams_dedup_insert_host", "yams_dedup_probe_host",
     "yams_cdc_chunk_device", "yams_ingest_device", "yams_ingest_host", "yams_cdc_chunk_host", "yams_cdc_chunk_window_host",
+    "yams_crc32_combine", "yams_crc32_batch_device", "yams_crc32_chunks_device", "yams_crc32_verify_device", "yams_crc32_many_host", "yams_ingest_host_crc32",
     "yams_plugin_get_abi_version", "yams_plugin_get_name", "yams_plugin_get_version",
     "yams_plugin_get_manifest_json", "yams_plugin_init", "yams_plugin_shutdown",
     "yams_plugin_get_interface", "yams_plugin_get_health_json",
@@ -436,6 +449,13 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
                                       C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.yams_cdc_chunk_window_host.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(CdcConfig), u64p, u64p,
                                              C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.yams_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+    L.yams_crc32_combine.restype = C.c_uint32
+    L.yams_crc32_batch_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp]
+    L.yams_crc32_chunks_device.argtypes = [vp, vp, u64p, C.c_uint64, C.POINTER(IngestResult), vp, vp]
+    L.yams_crc32_verify_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, u64p]
+    L.yams_crc32_many_host.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, u32p]
+    L.yams_ingest_host_crc32.argtypes = L.yams_ingest_host.argtypes + [vp]
     L.yams_plugin_get_abi_version.restype = C.c_int
     L.yams_plugin_get_name.restype = C.c_char_p
     L.yams_plugin_get_version.restype = C.c_char_p

@@ -708,6 +708,40 @@ class Accel:
         self._check(self.L.yams_sha256_batch_device(self.ctx, data_ptr, offsets_ptr, lengths_ptr,
                                                     n, digests_ptr))
 
+    # ---- CRC-32 (the compressed store's header checksum) ------------------------------------------------
+    def crc32_combine(self, crc_a: int, crc_b: int, len_b: int) -> int:
+        return int(self.L.yams_crc32_combine(crc_a, crc_b, len_b))
+
+    def crc32_many(self, msgs: list) -> np.ndarray:
+        """yams_crc32_many_host: CRC-32 of every message (bytes / uint8 arrays / None for an empty one) -> uint32[n]."""
+        arrs = [np.zeros(0, np.uint8) if m is None else np.frombuffer(bytes(m), np.uint8) if not isinstance(m, np.ndarray)
+                else np.ascontiguousarray(m, np.uint8) for m in msgs]
+        n = len(arrs)
+        out = np.zeros(n, np.uint32)
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        self._check(self.L.yams_crc32_many_host(self.ctx, ptrs, lens, n, out.ctypes.data_as(_lib.u32p)))
+        return out
+
+    def crc32(self, data) -> int:
+        return int(self.crc32_many([data])[0])
+
+    def crc32_batch_device(self, data_ptr, offsets_ptr, lengths_ptr, n, out_ptr):
+        self._check(self.L.yams_crc32_batch_device(self.ctx, data_ptr, offsets_ptr, lengths_ptr, n, out_ptr))
+
+    def crc32_chunks_device(self, data_ptr, blob_offsets, res: IngestResult, out_ptr, select_ptr=None):
+        """The chunks of an ingest result over the same data and blob offsets; select_ptr: device u8[n_chunks] or None."""
+        bo = np.ascontiguousarray(blob_offsets, np.uint64)
+        self._check(self.L.yams_crc32_chunks_device(self.ctx, data_ptr, bo.ctypes.data_as(_lib.u64p), bo.size, C.byref(res),
+                                                    select_ptr, out_ptr))
+
+    def crc32_verify_device(self, data_ptr, offsets_ptr, lengths_ptr, n, expected_ptr, valid_ptr) -> int:
+        """out_valid[i] = (crc == expected[i]); returns the number of mismatching messages."""
+        bad = C.c_uint64(0)
+        self._check(self.L.yams_crc32_verify_device(self.ctx, data_ptr, offsets_ptr, lengths_ptr, n, expected_ptr, valid_ptr,
+                                                    C.byref(bad)))
+        return bad.value
+
     # ---- chunking / ingest ----------------------------------------------------------------------
     def verify_chunks_device(self, data_ptr, offsets_ptr, lengths_ptr, n, expected_ptr, valid_ptr) -> int:
         """Batched integrity check; returns the number of mismatching chunks."""
@@ -754,9 +788,10 @@ class Accel:
         return res
 
     def ingest_host(self, blob_ptrs, blob_lengths, cfg: CdcConfig | None = None, flags: int = 3,
-                    batch_bytes: int = 0, chunk_cap: int | None = None) -> dict:
+                    batch_bytes: int = 0, chunk_cap: int | None = None, with_crc32: bool = False) -> dict:
         """yams_ingest_host: blobs in host memory (addresses in blob_ptrs), streamed through the device
-        in batches.  Returns blob_first, chunk_offset, chunk_size, chunk_digest, blob_digest (numpy)."""
+        in batches.  Returns blob_first, chunk_offset, chunk_size, chunk_digest, blob_digest (numpy).
+        with_crc32: yams_ingest_host_crc32 — the same call plus chunk_crc32 (uint32 per chunk)."""
         cfg = cfg or cdc_config()
         bl = np.ascontiguousarray(blob_lengths, np.uint64)
         n = int(bl.size)
@@ -768,15 +803,20 @@ class Accel:
         dg = np.empty((chunk_cap, 32), np.uint8) if flags & 1 else None
         bd = np.empty((n, 32), np.uint8) if flags & 2 else None
         cnt = C.c_uint64(0)
-        rc = self.L.yams_ingest_host(self.ctx, ptrs, bl.ctypes.data_as(_lib.u64p), n, C.byref(cfg), flags, batch_bytes,
-                                     first.ctypes.data_as(_lib.u64p), off.ctypes.data_as(_lib.u64p),
-                                     sz.ctypes.data_as(_lib.u64p), dg.ctypes.data if dg is not None else None,
-                                     chunk_cap, bd.ctypes.data if bd is not None else None, C.byref(cnt))
+        args = [self.ctx, ptrs, bl.ctypes.data_as(_lib.u64p), n, C.byref(cfg), flags, batch_bytes,
+                first.ctypes.data_as(_lib.u64p), off.ctypes.data_as(_lib.u64p),
+                sz.ctypes.data_as(_lib.u64p), dg.ctypes.data if dg is not None else None,
+                chunk_cap, bd.ctypes.data if bd is not None else None, C.byref(cnt)]
+        crc = np.empty(chunk_cap, np.uint32) if with_crc32 else None
+        rc = self.L.yams_ingest_host_crc32(*args, crc.ctypes.data) if with_crc32 else self.L.yams_ingest_host(*args)
         self.last_required_chunks = int(cnt.value)
         self._check(rc)
         m = int(cnt.value)
-        return {"n_chunks": m, "blob_first": first, "chunk_offset": off[:m], "chunk_size": sz[:m],
-                "chunk_digest": dg[:m] if dg is not None else None, "blob_digest": bd}
+        out = {"n_chunks": m, "blob_first": first, "chunk_offset": off[:m], "chunk_size": sz[:m],
+               "chunk_digest": dg[:m] if dg is not None else None, "blob_digest": bd}
+        if with_crc32:
+            out["chunk_crc32"] = crc[:m]
+        return out
 
     def download(self, ptr: int, dtype, count: int) -> np.ndarray:
         out = np.empty(count, dtype=dtype)

@@ -272,12 +272,13 @@ yams_status_t yams_ingest_device(yams_accel_ctx* ctx, const uint8_t* data,
 // already on its way on a copy stream of its own; the results of a batch (a few bytes per chunk) go
 // back before the next one starts.  Small blobs: bound by the link.  Large blobs: a batch cannot end
 // before the SHA-256 chain of its longest blob has (one lane, ~35 MB/s), so batches are GiB-sized.
-yams_status_t yams_ingest_host(yams_accel_ctx* ctx, const uint8_t* const* blobs_host,
-                               const uint64_t* blob_lengths, uint64_t n_blobs,
-                               const yams_cdc_config_t* cfg, uint32_t flags, uint64_t batch_bytes,
-                               uint64_t* out_blob_first, uint64_t* out_chunk_offset,
-                               uint64_t* out_chunk_size, uint8_t* out_chunk_digest, uint64_t chunk_cap,
-                               uint8_t* out_blob_digest, uint64_t* out_n_chunks) {
+// (one implementation behind yams_ingest_host and yams_ingest_host_crc32: out_chunk_crc32 is the only difference — NULL for the former)
+static yams_status_t ingest_host_common(yams_accel_ctx* ctx, const uint8_t* const* blobs_host,
+                                        const uint64_t* blob_lengths, uint64_t n_blobs,
+                                        const yams_cdc_config_t* cfg, uint32_t flags, uint64_t batch_bytes,
+                                        uint64_t* out_blob_first, uint64_t* out_chunk_offset,
+                                        uint64_t* out_chunk_size, uint8_t* out_chunk_digest, uint64_t chunk_cap,
+                                        uint8_t* out_blob_digest, uint64_t* out_n_chunks, uint32_t* out_chunk_crc32) {
     if (!ctx) return YAMS_ERR_INVALID_ARG;
     if (out_n_chunks) *out_n_chunks = 0;
     if (n_blobs && (!blobs_host || !blob_lengths)) return fail(ctx, YAMS_ERR_INVALID_ARG, "null blob list");
@@ -502,13 +503,24 @@ yams_status_t yams_ingest_host(yams_accel_ctx* ctx, const uint8_t* const* blobs_
         const bool take = !too_small && r.n_chunks;
         const bool take_dg = take && out_chunk_digest && r.chunk_digest;
         const size_t b_first = (bt.count + 1) * 8, b_tab = take ? r.n_chunks * 8 : 0, b_dg = take_dg ? r.n_chunks * 32 : 0;
+        // yams_ingest_host_crc32: the CRC-32 of every chunk of the batch while its bytes are resident — one more pass
+        // (crc32_kernels.hip) and one more copy per batch
+        const bool take_crc = take && out_chunk_crc32;
+        const size_t b_crc = take_crc ? r.n_chunks * 4 : 0;
+        uint32_t* d_crc = nullptr;
+        if (take_crc) {
+            if ((rc = ws_get(ctx, "ing_chunk_crc", b_crc, (void**)&d_crc)) != YAMS_OK) break;
+            if ((rc = yams_crc32_chunks_device(ctx, d_buf[slot], offs.data(), bt.count, &r, nullptr, d_crc)) != YAMS_OK) break;
+        }
         unsigned char* stage;
-        if ((rc = pinned_get(ctx, b_first + 2 * b_tab + b_dg + 64, (void**)&stage)) != YAMS_OK) break;
+        if ((rc = pinned_get(ctx, b_first + 2 * b_tab + b_dg + b_crc + 64, (void**)&stage)) != YAMS_OK) break;
         unsigned char* s_first = stage; unsigned char* s_off = s_first + b_first; unsigned char* s_size = s_off + b_tab; unsigned char* s_dg = s_size + b_tab;
+        unsigned char* s_crc = s_dg + b_dg;
         if (!hip_ok(hipMemcpyAsync(s_first, r.blob_first, b_first, hipMemcpyDeviceToHost, st), "results")) break;
         if (take && (!hip_ok(hipMemcpyAsync(s_off, r.chunk_offset, b_tab, hipMemcpyDeviceToHost, st), "results") ||
                      !hip_ok(hipMemcpyAsync(s_size, r.chunk_size, b_tab, hipMemcpyDeviceToHost, st), "results"))) break;
         if (take_dg && !hip_ok(hipMemcpyAsync(s_dg, r.chunk_digest, b_dg, hipMemcpyDeviceToHost, st), "results")) break;
+        if (take_crc && !hip_ok(hipMemcpyAsync(s_crc, d_crc, b_crc, hipMemcpyDeviceToHost, st), "results")) break;
         if (chains) { pending[slot].open = true; pending[slot].d_digests = r.blob_digest; pending[slot].first = bt.first; pending[slot].count = bt.count; }
         YAMS_TRACE_T(t3);
         if (!hip_ok(hipStreamSynchronize(st), "sync")) break;
@@ -518,6 +530,7 @@ yams_status_t yams_ingest_host(yams_accel_ctx* ctx, const uint8_t* const* blobs_
             std::memcpy(out_chunk_offset + chunk_base, s_off, b_tab);
             std::memcpy(out_chunk_size + chunk_base, s_size, b_tab);
             if (take_dg) std::memcpy(out_chunk_digest + chunk_base * 32, s_dg, b_dg);
+            if (take_crc) std::memcpy(out_chunk_crc32 + chunk_base, s_crc, b_crc);
         }
         chunk_base += r.n_chunks;
 #ifdef YAMS_ACCEL_MEASURE
@@ -532,6 +545,28 @@ yams_status_t yams_ingest_host(yams_accel_ctx* ctx, const uint8_t* const* blobs_
     if (out_n_chunks) *out_n_chunks = chunk_base;
     if (too_small) return fail(ctx, YAMS_ERR_INVALID_ARG, "chunk arrays too small (out_n_chunks holds the required size)");
     return YAMS_OK;
+}
+
+yams_status_t yams_ingest_host(yams_accel_ctx* ctx, const uint8_t* const* blobs_host,
+                               const uint64_t* blob_lengths, uint64_t n_blobs,
+                               const yams_cdc_config_t* cfg, uint32_t flags, uint64_t batch_bytes,
+                               uint64_t* out_blob_first, uint64_t* out_chunk_offset,
+                               uint64_t* out_chunk_size, uint8_t* out_chunk_digest, uint64_t chunk_cap,
+                               uint8_t* out_blob_digest, uint64_t* out_n_chunks) {
+    return ingest_host_common(ctx, blobs_host, blob_lengths, n_blobs, cfg, flags, batch_bytes, out_blob_first, out_chunk_offset,
+                              out_chunk_size, out_chunk_digest, chunk_cap, out_blob_digest, out_n_chunks, nullptr);
+}
+
+yams_status_t yams_ingest_host_crc32(yams_accel_ctx* ctx, const uint8_t* const* blobs_host,
+                                     const uint64_t* blob_lengths, uint64_t n_blobs,
+                                     const yams_cdc_config_t* cfg, uint32_t flags, uint64_t batch_bytes,
+                                     uint64_t* out_blob_first, uint64_t* out_chunk_offset,
+                                     uint64_t* out_chunk_size, uint8_t* out_chunk_digest, uint64_t chunk_cap,
+                                     uint8_t* out_blob_digest, uint64_t* out_n_chunks, uint32_t* out_chunk_crc32) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    if (!out_chunk_crc32 && chunk_cap) return fail(ctx, YAMS_ERR_INVALID_ARG, "null out_chunk_crc32");
+    return ingest_host_common(ctx, blobs_host, blob_lengths, n_blobs, cfg, flags, batch_bytes, out_blob_first, out_chunk_offset,
+                              out_chunk_size, out_chunk_digest, chunk_cap, out_blob_digest, out_n_chunks, out_chunk_crc32);
 }
 
 yams_status_t yams_sha256_batch_device(yams_accel_ctx* ctx, const uint8_t* data,

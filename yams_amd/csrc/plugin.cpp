@@ -1,8 +1,8 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// seven interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, content_hash_v1, chunker_v1) written to the
+// eight interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
+// semantic_graph_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
@@ -1280,6 +1280,37 @@ yams_content_hash_v1 g_content_hash = {YAMS_IFACE_CONTENT_HASH_V1_VERSION, nullp
                                        GUARDED(ch_verify_many), GUARDED(ch_dedup_create), GUARDED(ch_dedup_insert),
                                        GUARDED(ch_dedup_contains), GUARDED(ch_dedup_size), GUARDED(ch_dedup_destroy)};
 
+// ---- content_checksum_v1: the compressed store's CRC-32 over host memory (yams_crc32_many_host) ------------------------------
+yams_status_t cs_crc32_many(void*, const uint8_t* const* msgs, const size_t* lens, size_t n, uint32_t* out) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    return yams_crc32_many_host(w.v, msgs, lens, n, out);
+}
+yams_status_t cs_crc32(void*, const uint8_t* data, size_t n, uint32_t* out) {
+    NEED_INIT();
+    if (!out || (n && !data)) return YAMS_ERR_INVALID_ARG;
+    const uint8_t* msgs[1] = {data};
+    const size_t lens[1] = {n};
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    return yams_crc32_many_host(w.v, msgs, lens, 1, out);
+}
+yams_status_t cs_verify_many(void*, const uint8_t* const* msgs, const size_t* lens, const uint32_t* expected, size_t n, uint8_t* out_valid) {
+    NEED_INIT();
+    if (n == 0) return YAMS_OK;
+    if (!msgs || !lens || !expected || !out_valid) return YAMS_ERR_INVALID_ARG;
+    std::vector<uint32_t> got(n);
+    {
+        Lease<yams_accel_ctx*> w(g.work_ctx);
+        const yams_status_t s = yams_crc32_many_host(w.v, msgs, lens, n, got.data());
+        if (s != YAMS_OK) return s;
+    }
+    for (size_t i = 0; i < n; ++i) out_valid[i] = got[i] == expected[i] ? 1 : 0;
+    return YAMS_OK;
+}
+
+yams_content_checksum_v1 g_content_checksum = {YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, nullptr, GUARDED(cs_crc32), GUARDED(cs_crc32_many),
+                                               GUARDED(cs_verify_many)};
+
 // ---- chunker_v1 -------------------------------------------------------------------------------
 yams_status_t ck_default_config(void*, uint32_t mode, yams_cdc_config_t* out_cfg) {
     if (!out_cfg || (mode != YAMS_CDC_RABIN && mode != YAMS_CDC_STREAMING)) return YAMS_ERR_INVALID_ARG;
@@ -1524,6 +1555,7 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
         {YAMS_IFACE_TOPOLOGY_CLUSTER_V1, YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION, &g_topology_cluster},
         {YAMS_IFACE_SEMANTIC_GRAPH_V1, YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION, &g_semantic_graph},
         {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
+        {YAMS_IFACE_CONTENT_CHECKSUM_V1, YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, &g_content_checksum},
         {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};
     for (const auto& f : kInterfaces)
         if (std::strcmp(iface_id, f.id) == 0) {
