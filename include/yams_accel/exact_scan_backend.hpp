@@ -138,12 +138,40 @@ public:
     // usesSimeonPqSearchEngine() (:1506-1560).  exact_fallback indexes (:3882-3893) keep calling searchSimilar.
     Result<void> setSimeonPqIndex(size_t dim, const std::vector<uint8_t>& codes, size_t m, const std::vector<std::string>& chunkIdOfIndex) {
         std::unique_lock lk(mu_);
-        return table_.setPqIndex(dim, codes, m, chunkIdOfIndex);
+        if (auto s = table_.setPqIndex(dim, codes, m, chunkIdOfIndex); !s) return s;
+        pqDim_ = dim;                             // (the index calibratePq reports on: the one set last)
+        return {};
+    }
+    // The order of the ADC sum is simeon's and NOT pinned here: ask the host's own scoring (pq_calibration.hpp) once an index
+    // is set, e.g.
+    //     backend.calibratePq([&](const float* table, const uint8_t* code, size_t m, float* out) { ... });
+    //     backend.calibratePqOnTable(pqQuery.table(), [&](const uint8_t* code, float* out) { *out = pqQuery.inner_product(code); return true; });
+    // Matched: searchSimeonPq runs in that order by default.  Not matched: it fails with ErrorCode::NotSupported and the host
+    // keeps its CPU loop.  Never asked: the sequential sum, counted (pqUncalibratedSearches) and warned about once per index.
+    Result<accel_pq::PqCalibration> calibratePq(const accel_pq::PqScoreFn& fn) {
+        std::unique_lock lk(mu_);
+        return table_.calibratePq(fn, pqDim_);
+    }
+    Result<accel_pq::PqCalibration> calibratePqOnTable(const std::vector<float>& table, const accel_pq::PqCodeScoreFn& codeFn) {
+        std::unique_lock lk(mu_);
+        return table_.calibratePqOnTable(table, codeFn, pqDim_);
+    }
+    Result<void> setPqSum(uint32_t flags) {
+        std::unique_lock lk(mu_);
+        return table_.setPqSum(flags);
+    }
+    PqSumSetting pqSum() const {
+        std::shared_lock lk(mu_);
+        return table_.pqSum(pqDim_);
+    }
+    uint64_t pqUncalibratedSearches() const {
+        std::shared_lock lk(mu_);
+        return table_.pqUncalibratedSearches();
     }
     Result<std::vector<VectorRecord>>
     searchSimeonPq(const std::vector<float>& query_embedding, const std::vector<float>& lut, size_t k, float similarity_threshold,
                    size_t rerank_factor, const std::vector<uint32_t>* candidate_indices = nullptr,
-                   uint32_t sum_flags = YAMS_PQ_SUM_SEQUENTIAL, VectorSearchDiagnostics* diagnostics = nullptr) {
+                   uint32_t sum_flags = accel_pq::kPqSumCalibrated, VectorSearchDiagnostics* diagnostics = nullptr) {
         if (query_embedding.empty() || k == 0) return std::vector<VectorRecord>{};                  // :3873-3875
         return withSyncedMirror([&]() -> Result<std::vector<VectorRecord>> {
             auto r = table_.searchPqBatch({query_embedding}, {lut}, k, similarity_threshold, rerank_factor, candidate_indices, sum_flags, diagnostics);
@@ -467,6 +495,7 @@ private:
     mutable std::shared_mutex mu_;
     bool initialized_ = false, tables_ = false;
     size_t dim_ = 0;
+    size_t pqDim_ = 0;                            // the dimension of the PQ index set last (0: none)
     bool inTxn_ = false, mirrorStale_ = false, rewarmedInTxn_ = false;
     std::vector<Op> journal_;   // durable mode: mutations of the open transaction, applied to the mirror at commit
     std::vector<Undo> undo_;    // in-memory mode: how to put the previous rows back on rollback

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "l2_calibration.hpp"
+#include "pq_calibration.hpp"
 #include "plugin.hpp"
 
 #ifdef YAMS_ACCEL_USE_HOST_TYPES
@@ -75,6 +76,17 @@ enum class ExactRowSelection { TopK, AllMatching }; // sqlite_vec_backend.cpp:34
 struct L2Setting {
     bool calibrated = false, matched = false;
     uint32_t flags = 0;
+    std::string detail;
+};
+
+// The product-quantised engine: the order of the ADC sum, as settled by calibratePq (pq_calibration.hpp) on the index's own
+// m.  Uncalibrated: searches with the default flag word run the sequential sum, are counted and warn once per index.
+// Calibrated and matched: that YAMS_PQ_SUM_* word goes with every such search.  Calibrated and NOT matched: they are refused
+// (ErrorCode::NotSupported).  A flag word the caller passes explicitly is always used as is.
+struct PqSumSetting {
+    bool calibrated = false, matched = false;
+    uint32_t flags = YAMS_PQ_SUM_SEQUENTIAL;
+    size_t m = 0;                 // the m the probe ran at
     std::string detail;
 };
 
@@ -560,6 +572,8 @@ public:
         if (m == 0 || codes.size() != n * m) return Error{ErrorCode::InvalidArgument, "codes must hold m bytes per indexed row"};
         if (auto sy = syncMirror(); !sy) return sy.error();   // (may compact: row numbers are final after it)
         pqChunkIds_ = chunkIdOfIndex; pqCodes_ = codes; pqM_ = m;
+        if (pqSum_.calibrated && pqSum_.m != m) recalibratePq(); // the host's function is kept: another m is another question
+        pqWarned_ = false;
         pqSerials_.assign(n, 0);                               // the row each index entry names NOW (0: none)
         for (size_t i = 0; i < n; ++i)
             if (const auto it = byId_.find(chunkIdOfIndex[i]); it != byId_.end()) pqSerials_[i] = serial_[it->second];
@@ -584,14 +598,31 @@ private:
     }
 public:
     // queries: RAW query embeddings; luts[q]: m x 256 floats, simeon::PQInnerProductQuery's table for the NORMALISED query
-    // (:3895-3901); candidateIndices (nullable): ascending indices into the PQ index (:3910-3937); sumFlags: YAMS_PQ_SUM_*.
+    // (:3895-3901); candidateIndices (nullable): ascending indices into the PQ index (:3910-3937); sumFlags: a YAMS_PQ_SUM_*
+    // word, used as is, or kPqSumCalibrated: the order calibratePq / setPqSum settled (refused when the host's order is not
+    // served; sequential, counted and warned about once per index when nobody asked).
     Result<std::vector<std::vector<VectorRecord>>>
     searchPqBatch(const std::vector<std::vector<float>>& queries, const std::vector<std::vector<float>>& luts, size_t k, float thr,
-                  size_t rerankFactor, const std::vector<uint32_t>* candidateIndices = nullptr, uint32_t sumFlags = YAMS_PQ_SUM_SEQUENTIAL,
+                  size_t rerankFactor, const std::vector<uint32_t>* candidateIndices = nullptr, uint32_t sumFlags = accel_pq::kPqSumCalibrated,
                   VectorSearchDiagnostics* diagnostics = nullptr) {
         if (!initialized_) return Error{ErrorCode::NotInitialized, "Database not initialized"};
         if (!vt_->search_pq) return Error{ErrorCode::NotImplemented, "plugin lacks search_pq (vector_scan_v1 version 2)"};
         if (queries.empty()) return std::vector<std::vector<VectorRecord>>{};
+        if (sumFlags == accel_pq::kPqSumCalibrated) {
+            if (pqSum_.calibrated && !pqSum_.matched)
+                return Error{ErrorCode::NotSupported, "the host's PQ sum order is not served: " + pqSum_.detail};
+            if (pqSum_.calibrated) {
+                sumFlags = pqSum_.flags;
+            } else {
+                sumFlags = YAMS_PQ_SUM_SEQUENTIAL;
+                ++pqUncalibratedSearches_;
+                if (!pqWarned_) {
+                    pqWarned_ = true;
+                    std::fprintf(stderr, "yams_accel: product-quantised search at dim %zu (m %zu) without calibration: the sequential sum is "
+                                         "used as is; call calibratePq(host scoring function) or setPqSum() to pin the order\n", dim_, pqM_);
+                }
+            }
+        }
         if (luts.size() != queries.size()) return Error{ErrorCode::InvalidArgument, "one table per query"};
         for (size_t i = 0; i < queries.size(); ++i)
             if (queries[i].size() != dim_ || luts[i].size() != pqM_ * 256)
@@ -632,9 +663,52 @@ public:
         return out;
     }
 
+    // Ask the HOST's own scoring function in which order it adds, on probes of THIS index's m (pq_calibration.hpp): on a match
+    // every later search with the default flag word carries that YAMS_PQ_SUM_*; on no match such searches fail with
+    // NotSupported.  The function is kept: an index of another m handed over later is probed again.  Returns the calibration
+    // record either way (Error only when no function was given or no PQ index is set).
+    Result<accel_pq::PqCalibration> calibratePq(const accel_pq::PqScoreFn& fn) {
+        if (!fn) return Error{ErrorCode::InvalidArgument, "calibratePq needs the host's scoring function"};
+        if (pqM_ == 0) return Error{ErrorCode::InvalidArgument, "calibratePq needs the PQ index (setPqIndex) first: the probes have its m"};
+        pqFn_ = fn; pqCodeFn_ = nullptr; pqCalTable_.clear();
+        return recalibratePq();
+    }
+    // The same for a host that can only score codes against the table of a query object it built (table: m x 256 floats).
+    Result<accel_pq::PqCalibration> calibratePqOnTable(const std::vector<float>& table, const accel_pq::PqCodeScoreFn& codeFn) {
+        if (!codeFn) return Error{ErrorCode::InvalidArgument, "calibratePqOnTable needs the host's scoring function"};
+        if (pqM_ == 0) return Error{ErrorCode::InvalidArgument, "calibratePqOnTable needs the PQ index (setPqIndex) first: the probes have its m"};
+        if (table.size() != pqM_ * 256) return Error{ErrorCode::InvalidArgument, "the table must hold m x 256 floats of the index's m"};
+        pqFn_ = nullptr; pqCodeFn_ = codeFn; pqCalTable_ = table;
+        return recalibratePq();
+    }
+    // Pin the order without a probe (a host that knows its build).  A word the device would refuse is refused here.
+    Result<void> setPqSum(uint32_t flags) {
+        if (!accel_pq::valid(flags)) return Error{ErrorCode::InvalidArgument, "YAMS_PQ_SUM_COMBINE_* / _TAIL_SCALAR need 4, 8 or 16 lanes"};
+        pqFn_ = nullptr; pqCodeFn_ = nullptr; pqCalTable_.clear();
+        pqSum_ = PqSumSetting{true, true, flags & YAMS_PQ_SUM_ORDER_MASK, pqM_, "set by the host: " + accel_pq::name(flags)};
+        return {};
+    }
+    const PqSumSetting& pqSum() const { return pqSum_; }
+    // PQ searches answered in an order nobody confirmed (the default flag word with no calibratePq / setPqSum before them)
+    uint64_t pqUncalibratedSearches() const { return pqUncalibratedSearches_; }
+    size_t pqM() const { return pqM_; }
+
 private:
+    accel_pq::PqCalibration recalibratePq() {
+        accel_pq::PqCalibration c;
+        if (pqFn_) c = accel_pq::calibratePq(pqFn_, pqM_);
+        else if (pqCodeFn_ && pqCalTable_.size() == pqM_ * 256) c = accel_pq::calibratePqOnTable(pqCalTable_.data(), pqM_, pqCodeFn_);
+        else if (pqCodeFn_) { c.m = pqM_; c.detail = "the calibration table has another m than the index now set (m " + std::to_string(pqM_) + "): calibratePqOnTable again"; }
+        else { pqSum_.m = pqM_; return c; }        // set by the host (setPqSum): a word holds at every m
+        pqSum_ = PqSumSetting{true, c.matched, c.flags, pqM_, c.detail};
+        return c;
+    }
     std::vector<std::string> pqChunkIds_; std::vector<uint8_t> pqCodes_; std::vector<uint64_t> pqSerials_; size_t pqM_ = 0;
     uint64_t pqGen_ = 0;          // mirrorGen_ when the device's index -> row table was derived
+    PqSumSetting pqSum_;
+    accel_pq::PqScoreFn pqFn_; accel_pq::PqCodeScoreFn pqCodeFn_; std::vector<float> pqCalTable_;
+    uint64_t pqUncalibratedSearches_ = 0;
+    bool pqWarned_ = false;
 
     // k above what one device call returns (YAMS_SCAN_MAX_K): the reference takes any k
     // (sqlite_vec_backend.cpp:4299-4303 keeps a heap of k), callers that over-fetch for fusion or re-ranking
@@ -761,11 +835,54 @@ public:
     Result<void> setPqIndex(size_t dim, const std::vector<uint8_t>& codes, size_t m, const std::vector<std::string>& chunkIdOfIndex) {
         auto idx = indexFor(dim);
         if (!idx) return idx.error();
-        return idx.value()->setPqIndex(codes, m, chunkIdOfIndex);
+        if (auto s = idx.value()->setPqIndex(codes, m, chunkIdOfIndex); !s) return s;
+        // the table's function reaches an index that had none yet (its own, if it has one, was asked again by setPqIndex)
+        if (!idx.value()->pqSum().calibrated) {
+            if (pqFn_) (void)idx.value()->calibratePq(pqFn_);
+            else if (pqSumSet_) (void)idx.value()->setPqSum(pqSumFlags_);
+        }
+        return {};
+    }
+    // One scoring function for the table: every PQ index set so far is probed at its own m, and so is every one set later.
+    // Returns the calibration of the PQ index of `dim` (0: the largest dimension that has one).  InvalidArgument when no PQ
+    // index is set (there is no m to probe at).
+    Result<accel_pq::PqCalibration> calibratePq(const accel_pq::PqScoreFn& fn, size_t dim = 0) {
+        if (!fn) return Error{ErrorCode::InvalidArgument, "calibratePq needs the host's scoring function"};
+        AccelVectorIndex* at = pqIndexAt(dim);
+        if (!at) return Error{ErrorCode::InvalidArgument, "calibratePq needs a PQ index (setPqIndex) first: the probes have its m"};
+        pqFn_ = fn; pqSumSet_ = false;
+        Result<accel_pq::PqCalibration> out = Error{ErrorCode::InvalidArgument, "no PQ index"};
+        for (auto& kv : byDim_)
+            if (kv.second->pqM() != 0) {
+                auto c = kv.second->calibratePq(fn);
+                if (kv.second.get() == at) out = std::move(c);
+            }
+        return out;
+    }
+    // The fixed-table form: the table belongs to ONE index (its m), so only the index of `dim` is calibrated.
+    Result<accel_pq::PqCalibration> calibratePqOnTable(const std::vector<float>& table, const accel_pq::PqCodeScoreFn& codeFn, size_t dim = 0) {
+        AccelVectorIndex* at = pqIndexAt(dim);
+        if (!at) return Error{ErrorCode::InvalidArgument, "calibratePqOnTable needs a PQ index (setPqIndex) first: the probes have its m"};
+        return at->calibratePqOnTable(table, codeFn);
+    }
+    Result<void> setPqSum(uint32_t flags) {
+        if (!accel_pq::valid(flags)) return Error{ErrorCode::InvalidArgument, "YAMS_PQ_SUM_COMBINE_* / _TAIL_SCALAR need 4, 8 or 16 lanes"};
+        pqFn_ = nullptr; pqSumSet_ = true; pqSumFlags_ = flags;
+        for (auto& kv : byDim_) (void)kv.second->setPqSum(flags);
+        return {};
+    }
+    PqSumSetting pqSum(size_t dim = 0) const {
+        const AccelVectorIndex* at = const_cast<AccelVectorTable*>(this)->pqIndexAt(dim);
+        return at ? at->pqSum() : PqSumSetting{};
+    }
+    uint64_t pqUncalibratedSearches() const {
+        uint64_t n = 0;
+        for (const auto& kv : byDim_) n += kv.second->pqUncalibratedSearches();
+        return n;
     }
     Result<std::vector<std::vector<VectorRecord>>>
     searchPqBatch(const std::vector<std::vector<float>>& queries, const std::vector<std::vector<float>>& luts, size_t k, float thr,
-                  size_t rerankFactor, const std::vector<uint32_t>* candidateIndices = nullptr, uint32_t sumFlags = YAMS_PQ_SUM_SEQUENTIAL,
+                  size_t rerankFactor, const std::vector<uint32_t>* candidateIndices = nullptr, uint32_t sumFlags = accel_pq::kPqSumCalibrated,
                   VectorSearchDiagnostics* diagnostics = nullptr) {
         if (queries.empty()) return std::vector<std::vector<VectorRecord>>{};
         const auto it = byDim_.find(queries.front().size());
@@ -869,6 +986,14 @@ public:
     }
 
 private:
+    AccelVectorIndex* pqIndexAt(size_t dim) {      // the index of `dim` if it has a PQ index; dim 0: the largest dimension that has
+        if (dim != 0) {
+            auto it = byDim_.find(dim);
+            return it != byDim_.end() && it->second->pqM() != 0 ? it->second.get() : nullptr;
+        }
+        for (auto it = byDim_.rbegin(); it != byDim_.rend(); ++it) if (it->second->pqM() != 0) return it->second.get();
+        return nullptr;
+    }
     Result<AccelVectorIndex*> indexFor(size_t dim) {
         auto it = byDim_.find(dim);
         if (it != byDim_.end()) return it->second.get();
@@ -900,6 +1025,8 @@ private:
     VectorSearchEngine engine_;
     L2Setting l2_;
     accel_l2::L2DistanceFn l2Fn_;
+    accel_pq::PqScoreFn pqFn_;
+    bool pqSumSet_ = false; uint32_t pqSumFlags_ = 0;
     std::map<size_t, std::unique_ptr<AccelVectorIndex>> byDim_;
     std::unordered_map<std::string, size_t> dimOf_;
 };

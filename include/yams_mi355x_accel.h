@@ -551,7 +551,8 @@ YAMS_ACCEL_API yams_status_t yams_synth_bytes_device(yams_accel_ctx* ctx, uint64
  * and hands over the codes once (a device mirror, appended like rows) and the tables per batch.  Per query the device
  *   1. scores every indexed row, or every index of `candidates` (:3910-3937, sorted ascending by the host), with
  *      approxScore = sum over j of lut[j][codes[index * m + j]] in fp32 (:3965-3977; the ORDER of the additions is
- *      simeon's: YAMS_PQ_SUM_* below — PARITY UNPINNED, simeon is absent from the reference checkout);
+ *      simeon's: YAMS_PQ_SUM_* below — nothing about simeon is pinned, it is absent from the reference checkout; the
+ *      host's own scoring function is probed instead, include/yams_accel/pq_calibration.hpp);
  *   2. keeps the best approxK = min(candidates, max(k, k * rerank_factor)) by (score desc, tie key asc) (:3952-3997);
  *   3. re-scores them with VectorDatabase::computeCosineSimilarity(raw query, row) in fp64, the reference's summation
  *      order (:4023-4034), drops similarity < threshold (:4036-4038);
@@ -577,12 +578,28 @@ typedef struct yams_scan_pq_index_s {
 #define YAMS_PQ_SUM_X8 2u         /* 8 partial sums (AVX-shaped)                                                                  */
 #define YAMS_PQ_SUM_X16 3u        /* 16 partial sums (AVX-512-shaped)                                                             */
 #define YAMS_PQ_SUM_MASK 3u
+/* bits 2-3 (4 / 8 / 16 lanes only): how the L partial sums p[0 .. L - 1] become one                                             */
+#define YAMS_PQ_SUM_COMBINE_LTR 0u                  /* s = 0; for l: s = s + p[l]                                                   */
+#define YAMS_PQ_SUM_COMBINE_HALVES (1u << 2)        /* for (w = L/2; w >= 1; w /= 2) for l < w: p[l] = p[l] + p[l + w]; p[0]
+                                                       (extract-high + add, then movehl / shuffle)                                  */
+#define YAMS_PQ_SUM_COMBINE_PAIRS (2u << 2)         /* for (w = L; w > 1; w /= 2) for l < w/2: p[l] = p[2l] + p[2l + 1]; p[0] (hadd)  */
+#define YAMS_PQ_SUM_COMBINE_HALVES4_PAIRS (3u << 2) /* HALVES while more than 4 lanes remain, then PAIRS on the last 4
+                                                       (extract-high, then movehdup + movehl)                                       */
+#define YAMS_PQ_SUM_COMBINE_MASK (3u << 2)
+/* bit 4 (4 / 8 / 16 lanes only): only elements j < (m / L) * L go through the lanes; the m % L others are added to the COMBINED
+ * sum one at a time in element order (a vector loop with a scalar remainder loop).  Without it they go into lanes j % L.        */
+#define YAMS_PQ_SUM_TAIL_SCALAR (1u << 4)
+#define YAMS_PQ_SUM_ORDER_MASK 0x1Fu
+/* 1 + 3 * 4 * 2 = 25 definitions (some coincide: 4 lanes under PAIRS and HALVES4_PAIRS, the tail bit when m % L == 0, ...).
+ * With YAMS_PQ_SUM_SEQUENTIAL every bit of 2-4 must be 0 (YAMS_ERR_INVALID_ARG, nothing written); bits above the mask are
+ * ignored.  Which one is the host's is not for the host to guess: include/yams_accel/pq_calibration.hpp asks its own
+ * scoring function and answers with one of these words, or with "none: refuse the engine". */
 
 typedef struct yams_scan_pq_params_s {
     uint32_t k;
     float similarity_threshold; /* on the EXACT similarity of the re-rank (:4036-4038)                                           */
     uint32_t rerank_factor;     /* SimeonPqIndexState::rerank_factor (>= 1; 0 is read as 1); k * rerank_factor <= 2047            */
-    uint32_t flags;             /* YAMS_PQ_SUM_*                                                                                  */
+    uint32_t flags;             /* YAMS_PQ_SUM_* (lanes | combine | tail)                                                         */
 } yams_scan_pq_params_t;
 
 /* corpus: the fp32 rows the re-rank reads (+ tie_rank / rank_row: the chunk_id order of the final sort; row_base / stripes:

@@ -607,12 +607,13 @@ class Accel:
 
     def scan_pq_topk(self, corpus: ScanCorpus, codes: np.ndarray, luts: np.ndarray, queries: np.ndarray, k: int, threshold: float = -1.0,
                      rerank_factor: int = 2, tie_keys: np.ndarray | None = None, row_of_index: np.ndarray | None = None,
-                     candidates: np.ndarray | None = None, sum_lanes: int = 1) -> ScanResult:
+                     candidates: np.ndarray | None = None, sum_lanes: int = 1, sum_flags: int | None = None) -> ScanResult:
         """The product-quantised engine's search (yams_scan_pq_topk_device; simeonPqSearchUnlocked, sqlite_vec_backend.cpp:
         3868-4056) from host arrays: codes u8 [n][m], luts f32 [nq][m][256] (what simeon's PQInnerProductQuery holds), raw
         queries [nq][dim], tie_keys u64 [n] (stableStringKey of the chunk ids), row_of_index u32 [n] (index -> corpus row),
         candidates: ascending indices or None.  The tie ranks and the key -> row table are derived here, as a host does once
-        per index build."""
+        per index build.  The order of the ADC sum: sum_lanes (1 / 4 / 8 / 16 lanes, added left to right), or sum_flags, a whole
+        YAMS_PQ_SUM_* word (lanes | combine | tail) that is passed as is and takes precedence."""
         codes = np.ascontiguousarray(codes, np.uint8)
         n, m = codes.shape
         q = np.ascontiguousarray(queries, np.float32)
@@ -642,7 +643,7 @@ class Accel:
             d_c = self.to_device(cand if n_c else np.zeros(1, np.uint32)); keep.append(d_c)
         kk = max(k, 1)
         d_s = self.alloc(nq * kk * 4); d_r = self.alloc(nq * kk * 8); d_n = self.alloc(nq * 4)
-        prm = _lib.ScanPqParams(k, threshold, rerank_factor, {1: 0, 4: 1, 8: 2, 16: 3}[sum_lanes])
+        prm = _lib.ScanPqParams(k, threshold, rerank_factor, {1: 0, 4: 1, 8: 2, 16: 3}[sum_lanes] if sum_flags is None else int(sum_flags))
         diag = ScanDiag()
         try:
             self._check(self.L.yams_scan_pq_topk_device(self.ctx, C.byref(corpus), C.byref(pq), d_q.ptr, d_l.ptr, nq, C.byref(prm),

@@ -816,7 +816,7 @@ yams_status_t vs_search_pq(void*, uint64_t id, const float* queries, const float
             if (yams_accel_upload(d.x, d_l, luts, static_cast<size_t>(nq) * p.m * 1024) != YAMS_OK ||
                 (candidates && yams_accel_upload(d.x, d_c, candidates, n_candidates * 4) != YAMS_OK)) return YAMS_ERR_INTERNAL;
             yams_scan_pq_index_t pi{p.codes, p.n, p.m, 0, p.tie_rank, p.key_row};
-            yams_scan_pq_params_t prm{k, threshold, rerank_factor, flags & YAMS_PQ_SUM_MASK};
+            yams_scan_pq_params_t prm{k, threshold, rerank_factor, flags & YAMS_PQ_SUM_ORDER_MASK};
             return yams_scan_pq_topk_device(d.x, d.view, &pi, d.d_q, d_l, nq, &prm, d_c, n_candidates, d.d_s, d.d_r, d.d_n, out_diag);
         });
 }

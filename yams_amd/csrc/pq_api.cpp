@@ -19,11 +19,11 @@ using namespace yams_accel;
 namespace yams_accel {
 hipError_t launch_pq_adc_keys(hipStream_t st, const uint8_t* codes, uint64_t n_codes, uint32_t m, const float* luts, const uint32_t* qmap,
                               uint32_t n_slots, int lanes, const uint32_t* tie_rank, const uint32_t* candidates, uint64_t n_items,
-                              uint64_t* keys, uint64_t key_stride);
+                              uint64_t* keys, uint64_t key_stride, uint32_t order);
 hipError_t launch_pq_adc_filter(hipStream_t st, int mode, const uint8_t* codes, uint64_t n_codes, uint32_t m, const float* luts,
                                 uint32_t n_slots, int lanes, const uint32_t* tie_rank, const uint32_t* candidates, uint64_t n_items,
                                 uint32_t stride, uint32_t* sample_out, uint32_t n_sample, const float* tau, uint32_t* list_count,
-                                uint64_t* list, uint32_t list_cap);
+                                uint64_t* list, uint32_t list_cap, uint32_t order);
 }
 
 extern "C" yams_status_t yams_scan_pq_topk_device(yams_accel_ctx* ctx, const yams_scan_corpus_t* corpus, const yams_scan_pq_index_t* pq,
@@ -35,6 +35,11 @@ extern "C" yams_status_t yams_scan_pq_topk_device(yams_accel_ctx* ctx, const yam
     if (diag) std::memset(diag, 0, sizeof(*diag));
     if (n_queries == 0) return YAMS_OK;
     if (!out_counts) return fail(ctx, YAMS_ERR_INVALID_ARG, "null out_counts");
+    const uint32_t lanes_flag = prm->flags & YAMS_PQ_SUM_MASK;
+    const int lanes = lanes_flag == YAMS_PQ_SUM_X4 ? 4 : (lanes_flag == YAMS_PQ_SUM_X8 ? 8 : (lanes_flag == YAMS_PQ_SUM_X16 ? 16 : 1));
+    // how the lanes become one and where the tail goes: meaningless for one lane, so refused there before anything is written
+    const uint32_t order = prm->flags & (YAMS_PQ_SUM_COMBINE_MASK | YAMS_PQ_SUM_TAIL_SCALAR);
+    if (lanes == 1 && order != 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "YAMS_PQ_SUM_COMBINE_* / YAMS_PQ_SUM_TAIL_SCALAR need 4, 8 or 16 lanes");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     const uint32_t nq = n_queries, dim = corpus->dim, k = prm->k;
@@ -55,8 +60,6 @@ extern "C" yams_status_t yams_scan_pq_topk_device(yams_accel_ctx* ctx, const yam
         return fail(ctx, YAMS_ERR_INVALID_ARG, "tie_rank and rank_row must be given together");
     if ((reinterpret_cast<uintptr_t>(pq->codes) & 3u) || (reinterpret_cast<uintptr_t>(luts) & 15u))
         return fail(ctx, YAMS_ERR_INVALID_ARG, "codes must be 4-byte and tables 16-byte aligned");
-    const uint32_t lanes_flag = prm->flags & YAMS_PQ_SUM_MASK;
-    const int lanes = lanes_flag == YAMS_PQ_SUM_X4 ? 4 : (lanes_flag == YAMS_PQ_SUM_X8 ? 8 : (lanes_flag == YAMS_PQ_SUM_X16 ? 16 : 1));
     // approxK (:3952-3960): max(k, k * rerank) unless that overflows, at most the candidates
     const uint64_t rf = std::max<uint32_t>(1u, prm->rerank_factor);
     const uint64_t budget = std::max<uint64_t>(k, static_cast<uint64_t>(k) * rf);
@@ -117,13 +120,13 @@ extern "C" yams_status_t yams_scan_pq_topk_device(yams_accel_ctx* ctx, const yam
         YA_HIP(ctx, hipMemsetAsync(d_lcount, 0, static_cast<size_t>(nq) * 4, st));
         { TimedRegion tr(ctx, "pq_adc_sample");
           YA_HIP(ctx, launch_pq_adc_filter(st, 1, pq->codes, pq->n_codes, pq->m, luts, nq, lanes, pq->tie_rank, candidates, n_items, stride,
-                                           d_sample, n_sample, nullptr, nullptr, nullptr, 0));
+                                           d_sample, n_sample, nullptr, nullptr, nullptr, 0, order));
           tr.end(); }
         ScanLaunch T; T.plan.n_queries = nq; T.plan.n_groups = n_sample; T.plan.tau_rank = rank; T.gmax = d_sample; T.tau_out = d_tau;
         YA_HIP(ctx, launch_select_tau(st, T, nullptr));
         { TimedRegion tr(ctx, "pq_adc");
           YA_HIP(ctx, launch_pq_adc_filter(st, 2, pq->codes, pq->n_codes, pq->m, luts, nq, lanes, pq->tie_rank, candidates, n_items, stride,
-                                           nullptr, n_sample, d_tau, d_lcount, d_list, list_cap));
+                                           nullptr, n_sample, d_tau, d_lcount, d_list, list_cap, order));
           tr.end(); }
         uint32_t* h_lc = h_pin + 2 * static_cast<size_t>(nq);
         YA_HIP(ctx, hipMemcpyAsync(h_lc, d_lcount, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToHost, st));
@@ -158,7 +161,7 @@ extern "C" yams_status_t yams_scan_pq_topk_device(yams_accel_ctx* ctx, const yam
             const uint32_t nb = std::min(batch, nt - b0);
             { TimedRegion tr(ctx, "pq_adc_keys");
               YA_HIP(ctx, launch_pq_adc_keys(st, pq->codes, pq->n_codes, pq->m, luts, d_qmap + b0, nb, lanes, pq->tie_rank, candidates, n_items,
-                                             d_keys, key_stride));
+                                             d_keys, key_stride, order));
               tr.end(); }
             const uint64_t* res; uint64_t res_stride;
             YA_HIP(ctx, launch_topk_keys(st, d_keys, key_stride, static_cast<uint32_t>(n_items), nb, approx_k, d_work, &res, &res_stride));

@@ -10,20 +10,73 @@
 //
 // The ORDER of the fp32 additions is simeon's (third_party/simeon is absent from the checkout): PARITY UNPINNED.  Served:
 // one sequential sum over j (LANES = 1) and 4 / 8 / 16 partial sums (element j -> lane j % LANES, lanes added left to
-// right) — the shapes a scalar loop and its SSE / AVX / AVX-512 forms take; the host picks the one its build reproduces
-// (the same idea as the L2 calibration: a crafted LUT separates them).
+// right) — the shapes a scalar loop and its SSE / AVX / AVX-512 forms take — and, for 4 / 8 / 16 lanes, the other ways a
+// vector loop ends: how the lanes become one (YAMS_PQ_SUM_COMBINE_*: left to right, halves = extract-high / movehl / shuffle,
+// pairs = hadd, halves down to 4 then pairs = extract-high / movehdup / movehl) and whether the m % LANES tail elements go
+// through the lanes or are added one by one AFTER the reduction (YAMS_PQ_SUM_TAIL_SCALAR).  The host does not pick: its own
+// scoring function is asked (include/yams_accel/pq_calibration.hpp), and an order that is none of these is refused.
+// `order` below is the flag word's combine and tail bits (flags & (YAMS_PQ_SUM_COMBINE_MASK | YAMS_PQ_SUM_TAIL_SCALAR)); the
+// lane count is the template parameter.  The order is wave-uniform and touches only the per-item epilogue: the main loop runs
+// to the BODY length (m, or m - m % LANES with the tail bit), the tail re-reads its <= 15 table entries from the LDS.
+// The kernels are instantiated twice per lane count: EXT = false for order == 0 (flag words 0 - 3: the body is m and the lanes
+// are added left to right at compile time — the instruction stream these words had before the other orders existed; with a
+// runtime body and the combine switch the 16-lane, four-query form, which sits at its 128-register cap, lost a quarter of its
+// speed) and EXT = true for every other word.
 #include "common.h"
 #include "scan_launch.h"
 
 namespace yams_accel {
 
+// p[0 .. LANES - 1] -> one sum, by the rule `comb` (YAMS_PQ_SUM_COMBINE_*).  Every index is a compile-time constant after
+// unrolling (the partial sums stay in registers); the switch is uniform over the launch.
+template <int LANES>
+__device__ __forceinline__ float pq_combine(const float (&p)[LANES], uint32_t comb) {
+    if constexpr (LANES == 1) {
+        return p[0];
+    } else {
+        float r[LANES];
+#pragma unroll
+        for (int l = 0; l < LANES; ++l) r[l] = p[l];
+        if (comb == YAMS_PQ_SUM_COMBINE_HALVES) {
+#pragma unroll
+            for (int w = LANES / 2; w >= 1; w /= 2)
+#pragma unroll
+                for (int l = 0; l < w; ++l) r[l] = __fadd_rn(r[l], r[l + w]);
+            return r[0];
+        }
+        if (comb == YAMS_PQ_SUM_COMBINE_PAIRS) {
+#pragma unroll
+            for (int w = LANES; w > 1; w /= 2)
+#pragma unroll
+                for (int l = 0; l < w / 2; ++l) r[l] = __fadd_rn(r[2 * l], r[2 * l + 1]);
+            return r[0];
+        }
+        if (comb == YAMS_PQ_SUM_COMBINE_HALVES4_PAIRS) {
+#pragma unroll
+            for (int w = LANES / 2; w >= 4; w /= 2)
+#pragma unroll
+                for (int l = 0; l < w; ++l) r[l] = __fadd_rn(r[l], r[l + w]);
+            return __fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3]));
+        }
+        float sc = 0.f;
+#pragma unroll
+        for (int l = 0; l < LANES; ++l) sc = __fadd_rn(sc, r[l]);
+        return sc;
+    }
+}
+// the length of the part of a code that goes through the lanes
+template <int LANES, bool EXT>
+__device__ __forceinline__ uint32_t pq_body(uint32_t m, uint32_t order) {
+    return (EXT && LANES > 1 && (order & YAMS_PQ_SUM_TAIL_SCALAR)) ? m - m % LANES : m;
+}
+
 // One workgroup: QG queries (their tables in LDS) x a run of indices.  Thread t scores indices t, t + 256, ... of the run
 // against all QG tables: a code byte is read once per QG queries.
-template <int LANES>
+template <int LANES, bool EXT>
 __global__ __launch_bounds__(256) void pq_adc_keys_kernel(const uint8_t* codes, uint64_t n_codes, uint32_t m, const float* luts,
                                                           const uint32_t* qmap, uint32_t n_slots, uint32_t qg,
                                                           const uint32_t* tie_rank, const uint32_t* candidates, uint64_t n_items,
-                                                          uint32_t run, uint64_t* keys, uint64_t key_stride) {
+                                                          uint32_t run, uint64_t* keys, uint64_t key_stride, uint32_t order) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* lut = reinterpret_cast<float*>(smem);                 // [qg][m][256]
     const uint32_t slot0 = blockIdx.y * qg;
@@ -38,6 +91,7 @@ __global__ __launch_bounds__(256) void pq_adc_keys_kernel(const uint8_t* codes, 
     __syncthreads();
     const uint64_t i0 = static_cast<uint64_t>(blockIdx.x) * run;
     const uint64_t i1 = i0 + run < n_items ? i0 + run : n_items;
+    const uint32_t body = pq_body<LANES, EXT>(m, order), comb = order & YAMS_PQ_SUM_COMBINE_MASK;
     for (uint64_t it = i0 + threadIdx.x; it < i1; it += 256) {
         const uint64_t idx = candidates ? candidates[it] : it;
         const bool live = idx < n_codes;
@@ -50,7 +104,7 @@ __global__ __launch_bounds__(256) void pq_adc_keys_kernel(const uint8_t* codes, 
         // sixteen sub-quantisers at a time: the partial-sum lane of element j is j % LANES — a compile-time constant inside the
         // unrolled group (LANES divides 16), so the partial sums stay in registers
         const bool words = (m & 3u) == 0;
-        for (uint32_t j0 = 0; j0 < m; j0 += 16) {
+        for (uint32_t j0 = 0; j0 < body; j0 += 16) {
             uint32_t w[4] = {0u, 0u, 0u, 0u};
             if (words) {
 #pragma unroll
@@ -63,7 +117,7 @@ __global__ __launch_bounds__(256) void pq_adc_keys_kernel(const uint8_t* codes, 
             }
 #pragma unroll
             for (int jj = 0; jj < 16; ++jj) {
-                if (j0 + jj >= m) break;
+                if (j0 + jj >= body) break;
                 const uint32_t c = (w[jj >> 2] >> (8 * (jj & 3))) & 255u;
                 const uint32_t o = (j0 + jj) * 256u + c;
 #pragma unroll
@@ -75,11 +129,25 @@ __global__ __launch_bounds__(256) void pq_adc_keys_kernel(const uint8_t* codes, 
             }
         }
         const uint32_t kidx = tie_rank ? tie_rank[live ? idx : 0] : static_cast<uint32_t>(idx);
+        float ext[4] = {0.f, 0.f, 0.f, 0.f};                     // EXT: the lanes combined by the rule, then the scalar tail
+        if constexpr (EXT) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) ext[s] = pq_combine<LANES>(part[s], comb);
+            // (YAMS_PQ_SUM_TAIL_SCALAR) elements body .. m - 1, one by one, after the reduction
+            for (uint32_t j = body; j < m; ++j) {
+                const uint32_t o = j * 256u + code[j];
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if (static_cast<uint32_t>(s) < nq_here) ext[s] = __fadd_rn(ext[s], lut[static_cast<uint64_t>(s) * lut_floats + o]);
+            }
+        }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
             if (static_cast<uint32_t>(s) < nq_here) {
                 float sc = part[s][0];
-                if (LANES > 1) {
+                if constexpr (EXT) {
+                    sc = ext[s];
+                } else if (LANES > 1) {
                     sc = 0.f;
 #pragma unroll
                     for (int l = 0; l < LANES; ++l) sc = __fadd_rn(sc, part[s][l]);
@@ -100,12 +168,12 @@ __global__ __launch_bounds__(256) void pq_adc_keys_kernel(const uint8_t* codes, 
 // below every code listed); a list that came out too short or too long sends its query through the unfiltered form above.
 // The tables of a query group are INTERLEAVED in LDS ([m][256][QG]): one ds_read_b128 per code byte serves four queries; a
 // workgroup is 1024 threads (the LDS holds one group's tables, so latency is hidden by waves, not by workgroups).
-template <int LANES, int QG, int MODE>
+template <int LANES, int QG, int MODE, bool EXT>
 __global__ __launch_bounds__(1024) void pq_adc_filter_kernel(const uint8_t* codes, uint64_t n_codes, uint32_t m, const float* luts,
                                                              uint32_t n_slots, const uint32_t* tie_rank, const uint32_t* candidates,
                                                              uint64_t n_items, uint32_t run, uint32_t stride, uint32_t* sample_out,
                                                              uint32_t n_sample, const float* tau, uint32_t* list_count, uint64_t* list,
-                                                             uint32_t list_cap) {
+                                                             uint32_t list_cap, uint32_t order) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* lut = reinterpret_cast<float*>(smem);                 // [m][256][QG]
     const uint32_t slot0 = blockIdx.y * QG;
@@ -127,6 +195,7 @@ __global__ __launch_bounds__(1024) void pq_adc_filter_kernel(const uint8_t* code
     const uint64_t i0 = static_cast<uint64_t>(blockIdx.x) * run;
     const uint64_t i1 = i0 + run < n_walk ? i0 + run : n_walk;
     const bool words = (m & 3u) == 0;
+    const uint32_t body = pq_body<LANES, EXT>(m, order), comb = order & YAMS_PQ_SUM_COMBINE_MASK;
     for (uint64_t it = i0 + threadIdx.x; it < i1; it += 1024) {
         const uint64_t item = MODE == 1 ? it * stride : it;
         const uint64_t idx = candidates ? candidates[item] : item;
@@ -142,7 +211,7 @@ __global__ __launch_bounds__(1024) void pq_adc_filter_kernel(const uint8_t* code
 #pragma unroll
             for (int l = 0; l < LANES; ++l) part2[s][l] = pq_f2{0.f, 0.f};
         const bool quads = words && (m & 15u) == 0 && ((reinterpret_cast<uintptr_t>(codes) & 15u) == 0);
-        for (uint32_t j0 = 0; j0 < m; j0 += 16) {
+        for (uint32_t j0 = 0; j0 < body; j0 += 16) {
             uint32_t w[4] = {0u, 0u, 0u, 0u};
             if (quads) {
                 const uint4 q4 = *reinterpret_cast<const uint4*>(code + j0);
@@ -158,7 +227,7 @@ __global__ __launch_bounds__(1024) void pq_adc_filter_kernel(const uint8_t* code
             }
 #pragma unroll
             for (int jj = 0; jj < 16; ++jj) {
-                if (j0 + jj >= m) break;
+                if (j0 + jj >= body) break;
                 const uint32_t c = (w[jj >> 2] >> (8 * (jj & 3))) & 255u;
                 const float* e = lut + static_cast<size_t>((j0 + jj) * 256u + c) * QG;
                 if constexpr (QG == 4) {
@@ -180,11 +249,27 @@ __global__ __launch_bounds__(1024) void pq_adc_filter_kernel(const uint8_t* code
             for (int l = 0; l < LANES; ++l) part[s][l] = (s & 1) ? part2[s >> 1][l].y : part2[s >> 1][l].x;
         uint32_t kidx = 0;
         if (MODE == 2) kidx = tie_rank ? tie_rank[live ? idx : 0] : static_cast<uint32_t>(idx);
+        float ext[QG];                                           // EXT: the lanes combined by the rule, then the scalar tail
+#pragma unroll
+        for (int s = 0; s < QG; ++s) ext[s] = 0.f;
+        if constexpr (EXT) {
+#pragma unroll
+            for (int s = 0; s < QG; ++s) ext[s] = pq_combine<LANES>(part[s], comb);
+            // (YAMS_PQ_SUM_TAIL_SCALAR) elements body .. m - 1, one by one, after the reduction (the tables of the slots past
+            // nq_here are zeros: their sums are never used)
+            for (uint32_t j = body; j < m; ++j) {
+                const float* e = lut + static_cast<size_t>(j * 256u + code[j]) * QG;
+#pragma unroll
+                for (int s = 0; s < QG; ++s) ext[s] = __fadd_rn(ext[s], e[s]);
+            }
+        }
 #pragma unroll
         for (int s = 0; s < QG; ++s)
             if (static_cast<uint32_t>(s) < nq_here) {
                 float sc = part[s][0];
-                if (LANES > 1) {
+                if constexpr (EXT) {
+                    sc = ext[s];
+                } else if (LANES > 1) {
                     sc = 0.f;
 #pragma unroll
                     for (int l = 0; l < LANES; ++l) sc = __fadd_rn(sc, part[s][l]);
@@ -200,14 +285,42 @@ __global__ __launch_bounds__(1024) void pq_adc_filter_kernel(const uint8_t* code
     }
 }
 
+struct PqFilterLaunch {
+    hipStream_t st; int mode; const uint8_t* codes; uint64_t n_codes; uint32_t m; const float* luts; uint32_t n_slots;
+    const uint32_t* tie_rank; const uint32_t* candidates; uint64_t n_items; uint32_t stride; uint32_t* sample_out; uint32_t n_sample;
+    const float* tau; uint32_t* list_count; uint64_t* list; uint32_t list_cap, order, qg, run; size_t sh; dim3 grid;
+};
+template <int L, int Q, int M, bool X>
+static hipError_t pq_filter_launch(const PqFilterLaunch& a) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pq_adc_filter_kernel<L, Q, M, X>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(a.sh));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((pq_adc_filter_kernel<L, Q, M, X>), a.grid, dim3(1024), a.sh, a.st, a.codes, a.n_codes, a.m, a.luts, a.n_slots, a.tie_rank,
+                       a.candidates, a.n_items, a.run, a.stride, a.sample_out, a.n_sample, a.tau, a.list_count, a.list, a.list_cap, a.order);
+    return hipSuccess;
+}
+// (a template, so that the form the launcher never picks — 16 lanes, four queries, the other orders — is not instantiated)
+template <int L, bool X>
+static hipError_t pq_filter_dispatch(const PqFilterLaunch& a) {
+    if constexpr (!(L == 16 && X)) {
+        if (a.qg == 4) return a.mode == 1 ? pq_filter_launch<L, 4, 1, X>(a) : pq_filter_launch<L, 4, 2, X>(a);
+    }
+    if (a.qg == 4) return hipErrorInvalidValue;
+    if (a.qg == 2) return a.mode == 1 ? pq_filter_launch<L, 2, 1, X>(a) : pq_filter_launch<L, 2, 2, X>(a);
+    return a.mode == 1 ? pq_filter_launch<L, 1, 1, X>(a) : pq_filter_launch<L, 1, 2, X>(a);
+}
+
 // mode 1: sample scores (sample_out [n_slots][n_sample], element i = item i * stride); mode 2: keys of the items that reach tau.
-// `luts` is the tables of slot 0 on (the caller offsets it): [n_slots][m][256].
+// `luts` is the tables of slot 0 on (the caller offsets it): [n_slots][m][256].  `order`: the flag word's combine and tail bits.
 hipError_t launch_pq_adc_filter(hipStream_t st, int mode, const uint8_t* codes, uint64_t n_codes, uint32_t m, const float* luts,
                                 uint32_t n_slots, int lanes, const uint32_t* tie_rank, const uint32_t* candidates, uint64_t n_items,
                                 uint32_t stride, uint32_t* sample_out, uint32_t n_sample, const float* tau, uint32_t* list_count,
-                                uint64_t* list, uint32_t list_cap) {
+                                uint64_t* list, uint32_t list_cap, uint32_t order) {
     if (n_items == 0 || n_slots == 0) return hipSuccess;
-    const uint32_t qg = static_cast<size_t>(m) * 4096u <= 144u * 1024u ? 4u : (static_cast<size_t>(m) * 2048u <= 144u * 1024u ? 2u : 1u);
+    uint32_t qg = static_cast<size_t>(m) * 4096u <= 144u * 1024u ? 4u : (static_cast<size_t>(m) * 2048u <= 144u * 1024u ? 2u : 1u);
+    // 16 lanes x 4 queries are 64 partial sums: the kernel sits at its 128-register cap and spills, and the combine switch of
+    // the other orders makes that worse (2.26 ms against 1.81 ms per 256 queries over 1M codes, m = 32) — they take two
+    // queries' tables per workgroup instead
+    if (order != 0 && lanes == 16 && qg == 4) qg = 2;
     if (static_cast<size_t>(qg) * m * 1024u > 144u * 1024u) return hipErrorInvalidValue; // m > 128 (checked by the caller)
     const size_t sh = static_cast<size_t>(qg) * m * 1024u;
     const uint64_t n_walk = mode == 1 ? n_sample : n_items;
@@ -215,28 +328,20 @@ hipError_t launch_pq_adc_filter(hipStream_t st, int mode, const uint8_t* codes, 
     uint32_t run = 65536;
     while (run > 4096 && (n_walk + run - 1) / run * ((n_slots + qg - 1) / qg) < 512) run >>= 1;
     const dim3 grid(static_cast<uint32_t>((n_walk + run - 1) / run), (n_slots + qg - 1) / qg);
-#define YAMS_PQF_LAUNCH(L, Q, M)                                                                                                   \
-    do {                                                                                                                           \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&pq_adc_filter_kernel<L, Q, M>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sh)); \
-        if (e_ != hipSuccess) return e_;                                                                                            \
-        hipLaunchKernelGGL((pq_adc_filter_kernel<L, Q, M>), grid, dim3(1024), sh, st, codes, n_codes, m, luts, n_slots, tie_rank,  \
-                           candidates, n_items, run, stride, sample_out, n_sample, tau, list_count, list, list_cap);              \
-    } while (0)
-#define YAMS_PQF_Q(L, M) do { if (qg == 4) YAMS_PQF_LAUNCH(L, 4, M); else if (qg == 2) YAMS_PQF_LAUNCH(L, 2, M); else YAMS_PQF_LAUNCH(L, 1, M); } while (0)
-#define YAMS_PQF_M(L) do { if (mode == 1) YAMS_PQF_Q(L, 1); else YAMS_PQF_Q(L, 2); } while (0)
-    if (lanes == 4) YAMS_PQF_M(4);
-    else if (lanes == 8) YAMS_PQF_M(8);
-    else if (lanes == 16) YAMS_PQF_M(16);
-    else YAMS_PQF_M(1);
-#undef YAMS_PQF_M
-#undef YAMS_PQF_Q
-#undef YAMS_PQF_LAUNCH
+    const PqFilterLaunch a{st, mode, codes, n_codes, m, luts, n_slots, tie_rank, candidates, n_items, stride, sample_out, n_sample, tau,
+                           list_count, list, list_cap, order, qg, run, sh, grid};
+    hipError_t e = hipSuccess;
+    if (lanes == 4) e = order == 0 ? pq_filter_dispatch<4, false>(a) : pq_filter_dispatch<4, true>(a);
+    else if (lanes == 8) e = order == 0 ? pq_filter_dispatch<8, false>(a) : pq_filter_dispatch<8, true>(a);
+    else if (lanes == 16) e = order == 0 ? pq_filter_dispatch<16, false>(a) : pq_filter_dispatch<16, true>(a);
+    else e = pq_filter_dispatch<1, false>(a);
+    if (e != hipSuccess) return e;
     return hipGetLastError();
 }
 
 hipError_t launch_pq_adc_keys(hipStream_t st, const uint8_t* codes, uint64_t n_codes, uint32_t m, const float* luts, const uint32_t* qmap,
                               uint32_t n_slots, int lanes, const uint32_t* tie_rank, const uint32_t* candidates, uint64_t n_items,
-                              uint64_t* keys, uint64_t key_stride) {
+                              uint64_t* keys, uint64_t key_stride, uint32_t order) {
     if (n_items == 0 || n_slots == 0) return hipSuccess;
     // tables of up to four queries per workgroup: 1 KiB per sub-quantiser and query, 128 KiB of the CU's LDS at most
     uint32_t qg = 4;
@@ -248,19 +353,21 @@ hipError_t launch_pq_adc_keys(hipStream_t st, const uint8_t* codes, uint64_t n_c
     uint32_t run = 16384;
     while (run > 1024 && (n_items + run - 1) / run * ((n_slots + qg - 1) / qg) < 1024) run >>= 1;
     const dim3 grid(static_cast<uint32_t>((n_items + run - 1) / run), (n_slots + qg - 1) / qg);
-#define YAMS_PQ_LAUNCH(L)                                                                                                          \
+#define YAMS_PQ_LAUNCH(L, X)                                                                                                       \
     do {                                                                                                                           \
         if (sh > 48u * 1024u) {                                                                                                    \
-            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&pq_adc_keys_kernel<L>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sh)); \
+            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&pq_adc_keys_kernel<L, X>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sh)); \
             if (e_ != hipSuccess) return e_;                                                                                        \
         }                                                                                                                          \
-        hipLaunchKernelGGL((pq_adc_keys_kernel<L>), grid, dim3(256), sh, st, codes, n_codes, m, luts, qmap, n_slots, qg, tie_rank, \
-                           candidates, n_items, run, keys, key_stride);                                                           \
+        hipLaunchKernelGGL((pq_adc_keys_kernel<L, X>), grid, dim3(256), sh, st, codes, n_codes, m, luts, qmap, n_slots, qg, tie_rank, \
+                           candidates, n_items, run, keys, key_stride, order);                                                    \
     } while (0)
-    if (lanes == 4) YAMS_PQ_LAUNCH(4);
-    else if (lanes == 8) YAMS_PQ_LAUNCH(8);
-    else if (lanes == 16) YAMS_PQ_LAUNCH(16);
-    else YAMS_PQ_LAUNCH(1);
+#define YAMS_PQ_X(L) do { if (order == 0) YAMS_PQ_LAUNCH(L, false); else YAMS_PQ_LAUNCH(L, true); } while (0)
+    if (lanes == 4) YAMS_PQ_X(4);
+    else if (lanes == 8) YAMS_PQ_X(8);
+    else if (lanes == 16) YAMS_PQ_X(16);
+    else YAMS_PQ_LAUNCH(1, false);
+#undef YAMS_PQ_X
 #undef YAMS_PQ_LAUNCH
     return hipGetLastError();
 }
