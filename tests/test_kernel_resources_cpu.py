@@ -82,6 +82,35 @@ def test_the_fp64_tile_kernels_keep_three_waves_their_lds_and_no_scratch(src, ke
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+@pytest.mark.parametrize("src,kernel,counters,waves", [
+    # entity_score_kernel: two counters per query; <1> and <4> ship at four waves per SIMD, <8> (17 fp64 sums per lane beside
+    # the eight float4 of the next chunk) at three
+    ("entity_kernels.hip", "entity_score_kernel", 2, {1: 4, 4: 4, 8: 3}),
+    # doc_score_kernel: one counter per query; the same core and the same classes — <8> gave up the fourth wave its 76
+    # registers allowed before it prefetched (DESIGN 3.7 has the measurement that accepted it)
+    ("doc_kernels.hip", "doc_score_kernel", 1, {1: 4, 4: 4, 8: 3})])
+def test_the_row_chain_kernels_keep_their_waves_their_lds_and_no_scratch(src, kernel, counters, waves):
+    """doc_score_kernel and entity_score_kernel share their staging and their chains (row_chains.h) as an inlined function.
+    All three forms of each (QG = 1, 4, 8 queries per workgroup) must exist, use no scratch (private segment 0, no register
+    spilled) and the static LDS the shared constants give: the padded rows, the query tile and the ordinals, plus the
+    kernel's own counters.  Registers: by the arithmetic of the fp64-tile case above (512 per lane, granules of 8), at most
+    128 leave four waves per SIMD — what the LDS of four workgroups per CU allows anyway — and at most 168 leave three."""
+    header = open(os.path.join(ROOT, "yams_amd", "csrc", "row_chains.h")).read()
+    c = {k: int(v) for k, v in re.findall(r"constexpr\s+int\s+(kRow\w+)\s*=\s*(\d+)\s*;", header)}
+    assert {"kRowThreads", "kRowChunk"} <= set(c), c      # (the row stride is the chunk padded by one float: the LDS figure below)
+    meta = {k: v for k, v in _metadata(_assembly(src)).items() if kernel in k}
+    assert len(meta) == 3, list(meta)
+    for qg, w in waves.items():
+        name = [k for k in meta if "%sILi%dEE" % (kernel, qg) in k]
+        assert len(name) == 1, (qg, list(meta))
+        m = meta[name[0]]
+        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (name, m)
+        lds = 4 * (c["kRowThreads"] * (c["kRowChunk"] + 1) + qg * c["kRowChunk"] + c["kRowThreads"] + counters * qg)
+        assert m["group_segment_fixed_size"] == lds, (name, m, lds)
+        assert m.get("agpr_count", 0) == 0 and m["vgpr_count"] <= {4: 128, 3: 168}[w], (name, m)
+
+
+@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
 @pytest.mark.parametrize("src", ["scan_i8_kernel.hip", "scan_bf16_kernel.hip"])
 def test_no_scratch_traffic_inside_the_mfma_loops(src):
     tiles = {k: v for k, v in _kernels(src).items() if "scan_tiles" in k}

@@ -10,25 +10,10 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "doc_launch.h"
 #include "scan_launch.h"
 
 using namespace yams_accel;
-
-namespace yams_accel { // doc_kernels.hip
-hipError_t launch_doc_score(hipStream_t st, const float* rows, uint64_t n_rows, uint32_t dim, const float* queries,
-                            const double* qnorm, uint32_t q0, uint32_t n_slots, const uint32_t* tie_rank,
-                            const uint32_t* row_mask, const uint32_t* rows_sel, const unsigned long long* n_sel_dev,
-                            uint64_t n_items, const uint32_t* row_doc, uint32_t n_docs, float threshold,
-                            unsigned long long* doc_key, unsigned long long* matching, uint32_t* bad_doc);
-hipError_t launch_doc_sel_keys(hipStream_t st, const unsigned long long* doc_key, const uint32_t* doc_rank, uint32_t n_docs,
-                               uint32_t n_slots, unsigned long long* sel);
-hipError_t launch_doc_rank_inverse(hipStream_t st, const uint32_t* doc_rank, uint32_t n_docs, uint32_t* inv, uint32_t* bad);
-hipError_t launch_doc_emit(hipStream_t st, const unsigned long long* res, uint64_t res_stride, const unsigned long long* doc_key,
-                           uint32_t n_docs, const float* rows, uint32_t dim, const float* queries, const double* qnorm,
-                           const uint32_t* rank_inv, const uint32_t* rank_row, int64_t row_base, uint32_t q0,
-                           uint32_t n_slots, uint32_t k, float* out_scores, int64_t* out_rows, uint32_t* out_docs,
-                           uint32_t* out_counts);
-}
 
 namespace {
 // bytes of per-document keys (doc_key + selection keys) one slice of queries may hold: 600 queries x 1 M documents run

@@ -8,8 +8,9 @@
 //   src/vector/sqlite_vec_backend.cpp:4253-4279   the fp64 cosine of every row (the fast path of the exact scan)
 //
 // Two launches per slice of queries:
-//   doc_score_kernel   every allowed row is read from HBM once per group of QG queries (row chunks staged through LDS with
-//                      16-byte loads), scored in fp64 in the reference's element order, counted, and its key
+//   doc_score_kernel   every allowed row is read from HBM once per group of QG queries (row_chains.h: 128-byte row chunks
+//                      staged through LDS with 16-byte loads, the next chunk's loads in flight while this one is summed),
+//                      scored in fp64 in the reference's element order, counted, and its key
 //                      pack_cosine_key(sim, tie rank) reduced per document: a segmented max over the runs of equal documents
 //                      inside a wave, then one atomicMax per run into doc_key[slot][doc]
 //   doc_sel_keys_kernel + topk_multilevel + doc_emit_kernel
@@ -17,14 +18,12 @@
 #include <algorithm>
 
 #include "common.h"
+#include "doc_launch.h"
+#include "row_chains.h"
 
 namespace yams_accel {
 
 namespace {
-
-constexpr int kDocThreads = 256;        // rows per workgroup (one per thread)
-constexpr int kDocChunk = 32;           // elements of a row per LDS stage (128 bytes)
-constexpr int kDocLds = kDocChunk + 1;  // padded LDS row stride (floats): thread t reads row t, conflict-free
 
 __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int off) {
     const uint32_t lo = __shfl_up(static_cast<uint32_t>(v), off, 64);
@@ -37,19 +36,19 @@ __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int off) {
 // One thread per allowed row (rows_sel: the compacted ordinals of a sparse allow-mask, bounded by *n_sel_dev; else every
 // row, skipping the clear bits of row_mask), QG queries per workgroup (blockIdx.y * QG + j of the slice).
 template <int QG>
-__global__ __launch_bounds__(kDocThreads) void doc_score_kernel(
+__global__ __launch_bounds__(kRowThreads) void doc_score_kernel(
     const float* __restrict__ rows, uint64_t n_rows, uint32_t dim, int vec4, const float* __restrict__ queries,
     const double* __restrict__ qnorm, uint32_t q0, uint32_t n_slots, const uint32_t* __restrict__ tie_rank,
     const uint32_t* __restrict__ row_mask, const uint32_t* __restrict__ rows_sel, const unsigned long long* n_sel_dev,
     uint64_t n_items, const uint32_t* __restrict__ row_doc, uint32_t n_docs, float threshold,
     unsigned long long* doc_key, unsigned long long* matching, uint32_t* bad_doc) {
-    __shared__ float s_rows[kDocThreads * kDocLds];
-    __shared__ float s_q[QG][kDocChunk];
-    __shared__ uint32_t s_row[kDocThreads];
+    __shared__ RowLdsRows s_rows;
+    __shared__ RowLdsQueries<QG> s_q;
+    __shared__ RowLdsOrdinals s_row;
     __shared__ uint32_t s_count[QG];
     const int t = threadIdx.x, lane = t & 63;
     const uint32_t slot0 = blockIdx.y * QG;
-    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kDocThreads + t;
+    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kRowThreads + t;
     const uint64_t n_valid = rows_sel ? (*n_sel_dev < n_items ? *n_sel_dev : n_items) : n_items;
     bool on = item < n_valid;
     uint64_t row = 0;
@@ -58,53 +57,11 @@ __global__ __launch_bounds__(kDocThreads) void doc_score_kernel(
         if (row >= n_rows) on = false;
         else if (!rows_sel && row_mask && !row_allowed(row_mask, row)) on = false;
     }
-    s_row[t] = on ? static_cast<uint32_t>(row) : 0xffffffffu;
     if (t < QG) s_count[t] = 0;
-    __syncthreads();
-
-    double nsq = 0.0, dot[QG];
-#pragma unroll
-    for (int j = 0; j < QG; ++j) dot[j] = 0.0;
-    for (uint32_t c0 = 0; c0 < dim; c0 += kDocChunk) {
-        const uint32_t cl = dim - c0 < static_cast<uint32_t>(kDocChunk) ? dim - c0 : static_cast<uint32_t>(kDocChunk);
-        // stage: 8 lanes per row, 16 bytes each -> a wave loads 8 rows x 128 contiguous bytes per instruction
-#pragma unroll 2
-        for (int it = 0; it < kDocChunk / 4; ++it) {
-            const int idx = it * kDocThreads + t;
-            const int rl = idx >> 3, v = (idx & 7) * 4;
-            const uint32_t r = s_row[rl];
-            float* dst = s_rows + rl * kDocLds + v;
-            if (r != 0xffffffffu && static_cast<uint32_t>(v) < cl) {
-                const float* src = rows + static_cast<uint64_t>(r) * dim + c0 + v;
-                if (vec4 && static_cast<uint32_t>(v) + 4 <= cl) {
-                    const float4 x = *reinterpret_cast<const float4*>(src);
-                    dst[0] = x.x; dst[1] = x.y; dst[2] = x.z; dst[3] = x.w;
-                } else {
-                    for (uint32_t e = 0; e < 4 && v + e < cl; ++e) dst[e] = src[e];
-                }
-            }
-        }
-        for (int i = t; i < QG * kDocChunk; i += kDocThreads) {
-            const int j = i / kDocChunk, e = i % kDocChunk;
-            const uint32_t slot = slot0 + j;
-            s_q[j][e] = (slot < n_slots && static_cast<uint32_t>(e) < cl)
-                            ? queries[static_cast<uint64_t>(q0 + slot) * dim + c0 + e] : 0.f;
-        }
-        __syncthreads();
-        if (on) {
-            const float* x = s_rows + t * kDocLds;
-            // the reference's order: one sequential chain per sum, element by element (:4253-4266); a product of two
-            // floats is exact in fp64, so fma == mul then add
-#pragma unroll 2
-            for (uint32_t i = 0; i < cl; ++i) {
-                const double sv = static_cast<double>(x[i]);
-                nsq = fma(sv, sv, nsq);
-#pragma unroll
-                for (int j = 0; j < QG; ++j) dot[j] = fma(sv, static_cast<double>(s_q[j][i]), dot[j]);
-            }
-        }
-        __syncthreads();
-    }
+    // the reference's sums (:4253-4266), one sequential chain each
+    double nsq, dot[QG];
+    row_chains<QG>(s_rows, s_q, s_row, on ? static_cast<uint32_t>(row) : kRowNone, rows, dim, vec4, queries, q0, slot0, n_slots,
+                   on, nsq, dot);
 
     // scores and keys: the fast path's rule (never the record path here)
     uint64_t key[QG];
@@ -223,16 +180,12 @@ hipError_t launch_doc_score(hipStream_t st, const float* rows, uint64_t n_rows, 
                             uint64_t n_items, const uint32_t* row_doc, uint32_t n_docs, float threshold,
                             unsigned long long* doc_key, unsigned long long* matching, uint32_t* bad_doc) {
     if (n_items == 0 || n_slots == 0) return hipSuccess;
-    const int vec4 = ((reinterpret_cast<uintptr_t>(rows) & 15u) == 0 && (dim & 3u) == 0) ? 1 : 0;
-    const uint32_t gx = static_cast<uint32_t>((n_items + kDocThreads - 1) / kDocThreads);
-#define YAMS_DOC_SCORE(QG)                                                                                                     \
-    hipLaunchKernelGGL((doc_score_kernel<QG>), dim3(gx, (n_slots + QG - 1) / QG), dim3(kDocThreads), 0, st, rows, n_rows,    \
-                       dim, vec4, queries, qnorm, q0, n_slots, tie_rank, row_mask, rows_sel, n_sel_dev, n_items, row_doc, n_docs, \
-                       threshold, doc_key, matching, bad_doc)
-    if (n_slots == 1) YAMS_DOC_SCORE(1);
-    else if (n_slots <= 4) YAMS_DOC_SCORE(4);
-    else YAMS_DOC_SCORE(8);
-#undef YAMS_DOC_SCORE
+    const int vec4 = row_vec4_loads(rows, dim);
+    row_chains_dispatch(n_items, n_slots, [&](auto qg, dim3 grid) {
+        hipLaunchKernelGGL((doc_score_kernel<decltype(qg)::value>), grid, dim3(kRowThreads), 0, st, rows, n_rows, dim, vec4, queries,
+                           qnorm, q0, n_slots, tie_rank, row_mask, rows_sel, n_sel_dev, n_items, row_doc, n_docs, threshold, doc_key,
+                           matching, bad_doc);
+    });
     return hipGetLastError();
 }
 

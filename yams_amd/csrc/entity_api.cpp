@@ -10,24 +10,10 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "entity_launch.h"
 #include "scan_launch.h"
 
 using namespace yams_accel;
-
-namespace yams_accel { // entity_kernels.hip
-hipError_t launch_entity_qnorm(hipStream_t st, const float* queries, uint32_t nq, uint32_t dim, double* qnorm);
-hipError_t launch_entity_compact(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows,
-                                 const yams_scan_entity_filter_t* filters, uint32_t n_filters,
-                                 const yams_scan_entities_t& cols, uint32_t* rows_sel, unsigned long long* counter);
-hipError_t launch_entity_score(hipStream_t st, const float* rows, uint64_t n_rows, uint32_t dim, const float* queries,
-                               const double* qnorm, const yams_scan_entity_filter_t* filters, uint32_t q0, uint32_t n_slots,
-                               const yams_scan_entities_t& cols, const uint32_t* rows_sel, const unsigned long long* n_sel_dev,
-                               uint64_t n_items, float threshold, unsigned long long* keys, unsigned long long* visited,
-                               unsigned long long* matching);
-hipError_t launch_entity_emit(hipStream_t st, const unsigned long long* res, uint64_t res_stride, const float* rows, uint32_t dim,
-                              const float* queries, const double* qnorm, int64_t row_base, uint32_t q0, uint32_t n_slots,
-                              uint32_t k, float* out_scores, int64_t* out_rows, uint32_t* out_counts);
-}
 
 namespace {
 // bytes of keys one slice of queries may hold (the budget of doc_api.cpp): 64 queries x 1 M rows run as two slices of 32
@@ -119,8 +105,8 @@ extern "C" yams_status_t yams_scan_entity_topk_device(yams_accel_ctx* ctx, const
         uint32_t* sel;
         YA_TRY(ws_get(ctx, "ent_rows_sel", static_cast<size_t>(corpus->n_rows) * 4, (void**)&sel));
         YA_TRY(ws_get(ctx, "ent_nsel", 8, (void**)&d_nsel));
-        YA_HIP(ctx, launch_entity_compact(st, corpus->row_mask, corpus->n_rows, n_uniq ? d_filt + nq : nullptr,
-                                          static_cast<uint32_t>(n_uniq), cols, sel, d_nsel));
+        YA_HIP(ctx, launch_compact_rows(st, corpus->row_mask, corpus->n_rows, n_uniq ? d_filt + nq : nullptr,
+                                        static_cast<uint32_t>(n_uniq), cols, sel, d_nsel));
         rows_sel = sel;
         // the admitted count comes back (8 bytes): keys, selection and the score grid are sized by it, not by the row count
         uint64_t* h_nsel = reinterpret_cast<uint64_t*>(h_pin + pin_body);

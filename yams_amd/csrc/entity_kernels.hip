@@ -15,40 +15,18 @@
 //   compact_rows_kernel     (scan_kernels.hip) only when a row_mask or the filters restrict the rows: the ordinals some
 //                           query admits
 //   per slice of queries:
-//   entity_score_kernel     every admitted row is read from HBM once per group of QG queries (128-byte row chunks staged
-//                           through LDS with 16-byte loads, the next chunk's loads in flight while this one is summed),
+//   entity_score_kernel     every admitted row is read from HBM once per group of QG queries (row_chains.h: 128-byte row
+//                           chunks staged through LDS with 16-byte loads, the next chunk's loads in flight while this one is summed),
 //                           scored, counted, and its key pack_key(similarity with -0.0 -> +0.0, row) written
 //   topk_multilevel + entity_emit_kernel   the k best keys of each query and their rows; a winner whose similarity is a
 //                           zero is scored again for the sign of its zero (the key holds the canonical one)
 #include <algorithm>
 
 #include "common.h"
-#include "scan_launch.h"
+#include "entity_launch.h"
+#include "row_chains.h"
 
 namespace yams_accel {
-
-namespace {
-
-constexpr int kEntThreads = 256;        // rows per workgroup (one per thread)
-constexpr int kEntChunk = 32;           // elements of a row per LDS stage (128 bytes)
-constexpr int kEntLds = kEntChunk + 1;  // padded LDS row stride (floats): thread t reads row t, conflict-free
-constexpr int kEntLoads = kEntChunk / 4; // 16-byte loads per thread and stage: 8 lanes per row, 32 rows per pass, 8 passes
-
-// up to four consecutive floats of a row (zero-filled past `left`), as one 16-byte load when the layout allows it
-__device__ __forceinline__ float4 entity_load4(const float* src, uint32_t left, int vec4) {
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (vec4 && left >= 4) {
-        x = *reinterpret_cast<const float4*>(src);
-    } else {
-        if (left > 0) x.x = src[0];
-        if (left > 1) x.y = src[1];
-        if (left > 2) x.z = src[2];
-        if (left > 3) x.w = src[3];
-    }
-    return x;
-}
-
-} // namespace
 
 // qnorm[q] = sqrt(sum of squares), fp64, element by element (norm_a of :1798,1802).  One thread per query.
 __global__ __launch_bounds__(64) void entity_qnorm_kernel(const float* __restrict__ queries, uint32_t nq, uint32_t dim,
@@ -67,21 +45,21 @@ __global__ __launch_bounds__(64) void entity_qnorm_kernel(const float* __restric
 // One thread per item (rows_sel: the compacted ordinals, bounded by *n_sel_dev; else item == row), QG queries per workgroup
 // (blockIdx.y * QG + j of the slice).  keys[slot][item] for every item < n_items: 0 = not kept.
 template <int QG>
-__global__ __launch_bounds__(kEntThreads) void entity_score_kernel(
+__global__ __launch_bounds__(kRowThreads) void entity_score_kernel(
     const float* __restrict__ rows, uint64_t n_rows, uint32_t dim, int vec4, const float* __restrict__ queries,
     const double* __restrict__ qnorm, const yams_scan_entity_filter_t* __restrict__ filters, uint32_t q0, uint32_t n_slots,
     const uint8_t* __restrict__ row_type, const uint32_t* __restrict__ row_node_type, const uint32_t* __restrict__ row_doc,
     const uint32_t* __restrict__ rows_sel, const unsigned long long* n_sel_dev, uint64_t n_items, float threshold,
     unsigned long long* __restrict__ keys, unsigned long long* visited, unsigned long long* matching) {
-    __shared__ float s_rows[kEntThreads * kEntLds];
-    __shared__ float s_q[QG][kEntChunk];
-    __shared__ uint32_t s_row[kEntThreads];
+    __shared__ RowLdsRows s_rows;
+    __shared__ RowLdsQueries<QG> s_q;
+    __shared__ RowLdsOrdinals s_row;
     __shared__ uint32_t s_count[2][QG];
     const int t = threadIdx.x, lane = t & 63;
     const uint32_t slot0 = blockIdx.y * QG;
-    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kEntThreads + t;
+    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kRowThreads + t;
     const uint64_t n_valid = rows_sel ? (*n_sel_dev < n_items ? *n_sel_dev : n_items) : n_items;
-    if (static_cast<uint64_t>(blockIdx.x) * kEntThreads >= n_valid) { // (a compacted list shorter than its bound: empty keys)
+    if (static_cast<uint64_t>(blockIdx.x) * kRowThreads >= n_valid) { // (a compacted list shorter than its bound: empty keys)
         if (item < n_items) {
 #pragma unroll
             for (int j = 0; j < QG; ++j)
@@ -103,61 +81,11 @@ __global__ __launch_bounds__(kEntThreads) void entity_score_kernel(
         if (in && slot < n_slots && (!filters || entity_admits(filters[q0 + slot], row_type, row_node_type, row_doc, row))) adm |= 1u << j;
     }
     const bool on = adm != 0; // a row that no query of the group admits is never read
-    s_row[t] = on ? static_cast<uint32_t>(row) : 0xffffffffu;
     if (t < 2 * QG) s_count[t / QG][t % QG] = 0;
-    __syncthreads();
-
-    // stage geometry: 8 lanes per row, 16 bytes each -> a wave loads 8 rows x 128 contiguous bytes per instruction
-    const int v = (t & 7) * 4;
-    const float* src[kEntLoads];
-#pragma unroll
-    for (int it = 0; it < kEntLoads; ++it) {
-        const uint32_t r = s_row[it * (kEntThreads / 8) + (t >> 3)];
-        src[it] = r != 0xffffffffu ? rows + static_cast<uint64_t>(r) * dim + v : nullptr;
-    }
-    float4 pre[kEntLoads];
-    auto fetch = [&](uint32_t c0) {
-        const uint32_t cl = dim - c0 < static_cast<uint32_t>(kEntChunk) ? dim - c0 : static_cast<uint32_t>(kEntChunk);
-        const uint32_t left = static_cast<uint32_t>(v) < cl ? cl - v : 0u;
-#pragma unroll
-        for (int it = 0; it < kEntLoads; ++it)
-            pre[it] = (src[it] && left) ? entity_load4(src[it] + c0, left, vec4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    fetch(0);
-
-    double nsq = 0.0, dot[QG];
-#pragma unroll
-    for (int j = 0; j < QG; ++j) dot[j] = 0.0;
-    for (uint32_t c0 = 0; c0 < dim; c0 += kEntChunk) {
-        const uint32_t cl = dim - c0 < static_cast<uint32_t>(kEntChunk) ? dim - c0 : static_cast<uint32_t>(kEntChunk);
-#pragma unroll
-        for (int it = 0; it < kEntLoads; ++it) {
-            float* dst = s_rows + (it * (kEntThreads / 8) + (t >> 3)) * kEntLds + v;
-            dst[0] = pre[it].x; dst[1] = pre[it].y; dst[2] = pre[it].z; dst[3] = pre[it].w;
-        }
-        for (int i = t; i < QG * kEntChunk; i += kEntThreads) {
-            const int j = i / kEntChunk, e = i % kEntChunk;
-            const uint32_t slot = slot0 + j;
-            s_q[j][e] = (slot < n_slots && static_cast<uint32_t>(e) < cl)
-                            ? queries[static_cast<uint64_t>(q0 + slot) * dim + c0 + e] : 0.f;
-        }
-        __syncthreads();
-        // the next chunk's loads are issued before this chunk's fp64 chain and land in registers while it runs
-        if (c0 + kEntChunk < dim) fetch(c0 + kEntChunk);
-        if (on) {
-            const float* x = s_rows + t * kEntLds;
-            // the reference's order: one sequential chain per sum, element by element (:1796-1800); a product of two
-            // floats is exact in fp64, so fma == multiply then add
-#pragma unroll 4
-            for (uint32_t i = 0; i < cl; ++i) {
-                const double sv = static_cast<double>(x[i]);
-                nsq = fma(sv, sv, nsq);
-#pragma unroll
-                for (int j = 0; j < QG; ++j) dot[j] = fma(static_cast<double>(s_q[j][i]), sv, dot[j]);
-            }
-        }
-        __syncthreads();
-    }
+    // the reference's sums (:1796-1800), one sequential chain each
+    double nsq, dot[QG];
+    row_chains<QG>(s_rows, s_q, s_row, on ? static_cast<uint32_t>(row) : kRowNone, rows, dim, vec4, queries, q0, slot0, n_slots,
+                   on, nsq, dot);
 
 #pragma unroll
     for (int j = 0; j < QG; ++j) {
@@ -222,28 +150,18 @@ hipError_t launch_entity_qnorm(hipStream_t st, const float* queries, uint32_t nq
     return hipGetLastError();
 }
 
-hipError_t launch_entity_compact(hipStream_t st, const uint32_t* row_mask, uint64_t n_rows,
-                                 const yams_scan_entity_filter_t* filters, uint32_t n_filters,
-                                 const yams_scan_entities_t& cols, uint32_t* rows_sel, unsigned long long* counter) {
-    return launch_compact_rows(st, row_mask, n_rows, filters, n_filters, cols, rows_sel, counter);
-}
-
 hipError_t launch_entity_score(hipStream_t st, const float* rows, uint64_t n_rows, uint32_t dim, const float* queries,
                                const double* qnorm, const yams_scan_entity_filter_t* filters, uint32_t q0, uint32_t n_slots,
                                const yams_scan_entities_t& cols, const uint32_t* rows_sel, const unsigned long long* n_sel_dev,
                                uint64_t n_items, float threshold, unsigned long long* keys, unsigned long long* visited,
                                unsigned long long* matching) {
     if (n_items == 0 || n_slots == 0) return hipSuccess;
-    const int vec4 = ((reinterpret_cast<uintptr_t>(rows) & 15u) == 0 && (dim & 3u) == 0) ? 1 : 0;
-    const uint32_t gx = static_cast<uint32_t>((n_items + kEntThreads - 1) / kEntThreads);
-#define YAMS_ENTITY_SCORE(QG)                                                                                                  \
-    hipLaunchKernelGGL((entity_score_kernel<QG>), dim3(gx, (n_slots + QG - 1) / QG), dim3(kEntThreads), 0, st, rows, n_rows,  \
-                       dim, vec4, queries, qnorm, filters, q0, n_slots, cols.row_type, cols.row_node_type, cols.row_doc,      \
-                       rows_sel, n_sel_dev, n_items, threshold, keys, visited, matching)
-    if (n_slots == 1) YAMS_ENTITY_SCORE(1);
-    else if (n_slots <= 4) YAMS_ENTITY_SCORE(4);
-    else YAMS_ENTITY_SCORE(8);
-#undef YAMS_ENTITY_SCORE
+    const int vec4 = row_vec4_loads(rows, dim);
+    row_chains_dispatch(n_items, n_slots, [&](auto qg, dim3 grid) {
+        hipLaunchKernelGGL((entity_score_kernel<decltype(qg)::value>), grid, dim3(kRowThreads), 0, st, rows, n_rows, dim, vec4, queries, qnorm,
+                           filters, q0, n_slots, cols.row_type, cols.row_node_type, cols.row_doc, rows_sel, n_sel_dev, n_items,
+                           threshold, keys, visited, matching);
+    });
     return hipGetLastError();
 }
 
