@@ -853,6 +853,62 @@ YAMS_ACCEL_API yams_status_t yams_graph_semantic_neighbors_host(
     uint32_t* out_rows, float* out_sims, uint32_t* out_counts, float* out_inv_norm, yams_graph_diag_t* out_diag);
 
 /* ------------------------------------------------------------------------------------------ */
+/* SGC smoothing of the document embeddings over the neighbour graph                          */
+/* ------------------------------------------------------------------------------------------ */
+/* applySGCSmoothing (src/topology/topology_sgc.cpp:23-179 of the reference, header include/yams/topology/topology_sgc.h,
+ * Lean contract formal/topology/Yams/Topology/SGC.lean) runs between the semantic-neighbour graph and the clustering:
+ * `hops` rounds of X <- D^-1/2 (A + I) D^-1/2 X over every document embedding ("54k docs x 1024 dim", :127-129).  This
+ * entry is its degree pass and its hop loop (:114-161); the shell in front of them (early returns :25-50, admission
+ * :60-84, symmetrisation :86-112, the feature matrix :130-137, the write-back :163-168) is
+ * include/yams_accel/topology_sgc.hpp.
+ * THE ORDER OF A ROW'S LIST IS AN INPUT.  The reference accumulates each output element in fp32, one neighbour at a time,
+ * in the order in which its symmetrised lists were filled — the iteration order of a std::unordered_map (:106-111), a
+ * property of the host's standard library.  Another order gives other bits, so the host builds the lists and this entry
+ * keeps their order: every output element is ONE chain in one lane; no atomics, no split chains, no reduction over edges.
+ * The contract, restated from topology_sgc.cpp, over the list (row_offsets, cols, weights):
+ *   degree (:114-125)  deg[i] = 1.0 + the fp64 chain of double(w) over row i's edges in list order;
+ *             inv[i] = deg > 0 ? 1.0 / sqrt(deg) : 0.0 — a correctly rounded square root, then a correctly rounded divide
+ *             (not a reciprocal square root).
+ *   one hop (:140-161)  for every row i and dimension d: acc = float((inv[i] * inv[i]) * double(x[i][d])); then for each edge
+ *             (to, w) of row i in list order: scale = (double(w) * inv[i]) * inv[to]; an edge with scale == 0.0 is SKIPPED,
+ *             not added (adding +0.0f would turn a -0.0f accumulator into +0.0f); otherwise
+ *             acc = acc +f32 float(scale * double(x[to][d])): an fp64 product, a cast that rounds to nearest even, an fp32 add
+ *             with denormals kept.  Hop h + 1 reads the output of hop h.
+ * The list need not be symmetric; self-loops and repeated columns are computed as the formula says.  An fp32 overflow inside
+ * the hops is served as IEEE gives it (inf, and NaN from inf - inf): only non-finite INPUT is refused.
+ * Refused with YAMS_ERR_INVALID_ARG, found on the device before anything is written: row_offsets[0] != 0, an offset that
+ * decreases, a column >= n, a weight that is negative or not finite, a non-finite element of rows.
+ * n == 0: YAMS_OK, nothing written.  hops == 0: out = rows, bit for bit (nothing else is looked at).  dim == 0, null rows,
+ * out or row_offsets, out overlapping rows: YAMS_ERR_INVALID_ARG.  n >= 2^31, nnz (= row_offsets[n]) >= 2^32,
+ * dim > YAMS_SGC_MAX_DIM: YAMS_ERR_UNSUPPORTED.
+ *   rows         device [n][dim] fp32 (any float alignment; 16-byte aligned bases and dim % 4 == 0 get vector loads)
+ *   row_offsets  device [n + 1] uint64;  cols device [nnz] uint32;  weights device [nnz] fp32 — the order IS the sum order
+ *   out          device [n][dim] fp32; must not overlap rows
+ *   out_diag     host, nullable
+ * Work: a lane owns four consecutive dimensions of one row and walks the row's edges in order with the loads of four edges
+ * in flight; a row of YAMS_SGC_HUB_DEGREE edges or more is dealt one dimension per lane instead, so four times as many waves
+ * share its walk.  Workspace: n doubles, nnz doubles (the scales, computed once per edge), n uint32, and for hops >= 2 one
+ * n x dim fp32 buffer; the result lands in `out` whatever the parity of hops.  One 32-byte read-back (the refusal flags, nnz)
+ * sits between the checks and the hops.  The call synchronises the context's stream before returning. */
+#define YAMS_SGC_MAX_DIM 4096u
+#define YAMS_SGC_HUB_DEGREE 512u
+typedef struct yams_sgc_diag {
+    uint64_t nnz;                      /* row_offsets[n] */
+    uint64_t edges_skipped_zero_scale; /* edges whose scale is 0.0 (each is skipped in every hop) */
+    uint32_t max_degree;               /* the longest list */
+    uint32_t hops;
+    uint32_t hub_rows;                 /* rows of YAMS_SGC_HUB_DEGREE edges or more */
+    uint32_t reserved;
+} yams_sgc_diag_t;
+YAMS_ACCEL_API yams_status_t yams_graph_sgc_smooth_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint64_t* row_offsets,
+    const uint32_t* cols, const float* weights, uint32_t hops, float* out, yams_sgc_diag_t* out_diag);
+/* The same over host memory: rows, row_offsets, cols, weights and out are host arrays. */
+YAMS_ACCEL_API yams_status_t yams_graph_sgc_smooth_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint64_t* row_offsets,
+    const uint32_t* cols, const float* weights, uint32_t hops, float* out, yams_sgc_diag_t* out_diag);
+
+/* ------------------------------------------------------------------------------------------ */
 /* SHA-256                                                                                   */
 /* ------------------------------------------------------------------------------------------ */
 /* Digest n_msgs byte ranges of one device buffer: message i = data[offsets[i] .. +lengths[i]).
@@ -1277,6 +1333,21 @@ typedef struct yams_semantic_graph_v1 {
                                yams_graph_diag_t* out_diag);
     void (*free_neighbors)(void* self, uint32_t* rows, float* sims, uint32_t* counts, float* inv_norm);
 } yams_semantic_graph_v1;
+
+/* SGC smoothing (yams_graph_sgc_smooth_host) for a host that holds the document embeddings and the neighbour lists in
+ * its own memory.  A separate interface, version 1, served by yams_plugin_get_interface and NOT listed in the manifest,
+ * for the reason given at vector_doc_scan_v1.  Host memory in, host memory out. */
+#define YAMS_IFACE_TOPOLOGY_SMOOTH_V1 "topology_smooth_v1"
+#define YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION 1u
+typedef struct yams_topology_smooth_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION */
+    void* self;
+    /* `hops` rounds of smoothing of rows [n][dim] over the list (row_offsets [n + 1], cols, weights: the order of a row's
+     * edges is the order of its sums) into out [n][dim], the caller's array; out_diag nullable.  Statuses and limits of the
+     * flat entry. */
+    yams_status_t (*smooth)(void* self, const float* rows, uint64_t n, uint32_t dim, const uint64_t* row_offsets, const uint32_t* cols,
+                            const float* weights, uint32_t hops, float* out, yams_sgc_diag_t* out_diag);
+} yams_topology_smooth_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

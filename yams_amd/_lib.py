@@ -226,6 +226,24 @@ GRAPH_MAX_DIM, GRAPH_MAX_K = 4096, 64            # YAMS_GRAPH_MAX_DIM / _MAX_K
 GRAPH_FLAG_EXPLICIT_THRESHOLD = 1
 
 
+class SgcDiag(C.Structure):  # yams_sgc_diag_t
+    _fields_ = [("nnz", C.c_uint64), ("edges_skipped_zero_scale", C.c_uint64), ("max_degree", C.c_uint32), ("hops", C.c_uint32),
+                ("hub_rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
+
+
+class TopologySmoothV1(C.Structure):  # topology_smooth_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("smooth", C.CFUNCTYPE(ST, vp, f32p, C.c_uint64, C.c_uint32, u64p, u32p, f32p, C.c_uint32, f32p, C.POINTER(SgcDiag))),
+    ]
+
+
+SGC_MAX_DIM, SGC_HUB_DEGREE = 4096, 512          # YAMS_SGC_MAX_DIM / _HUB_DEGREE
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -294,6 +312,7 @@ EXPORTS = [
     "yams_scan_doc_topk_device", "yams_scan_entity_topk_device",
     "yams_cluster_kmeans_device", "yams_cluster_kmeans_host", "yams_cluster_assign_device",
     "yams_graph_semantic_neighbors_device", "yams_graph_semantic_neighbors_host",
+    "yams_graph_sgc_smooth_device", "yams_graph_sgc_smooth_host",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -387,6 +406,8 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
     for fn in (L.yams_graph_semantic_neighbors_device, L.yams_graph_semantic_neighbors_host):
         fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp,
                        C.POINTER(GraphDiag)]
+    for fn in (L.yams_graph_sgc_smooth_device, L.yams_graph_sgc_smooth_host):
+        fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, vp, C.POINTER(SgcDiag)]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

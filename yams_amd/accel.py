@@ -605,6 +605,45 @@ class Accel:
         """semantic_neighbors through yams_graph_semantic_neighbors_host (host arrays in, host arrays out)."""
         return self.semantic_neighbors(rows, k, host_entry=True, **kw)
 
+    def sgc_smooth_device(self, rows_ptr: int, n: int, dim: int, row_offsets_ptr: int, cols_ptr: int | None, weights_ptr: int | None,
+                          hops: int, out_ptr: int) -> dict:
+        """yams_graph_sgc_smooth_device over device arrays.  Returns the diagnostics {nnz, edges_skipped_zero_scale,
+        max_degree, hops, hub_rows}."""
+        diag = _lib.SgcDiag()
+        self._check(self.L.yams_graph_sgc_smooth_device(self.ctx, rows_ptr, n, dim, row_offsets_ptr, cols_ptr, weights_ptr, hops, out_ptr,
+                                                        C.byref(diag)))
+        return diag.as_dict()
+
+    def sgc_smooth(self, rows: np.ndarray, row_offsets: np.ndarray, cols: np.ndarray, weights: np.ndarray, hops: int,
+                   host_entry: bool = False):
+        """SGC smoothing (applySGCSmoothing's degree pass and hop loop) of host rows [n][dim] over the list (row_offsets [n + 1]
+        uint64, cols uint32, weights float32): the order of a row's edges is the order of its fp32 sums.  Returns (out [n][dim]
+        float32, diag).  host_entry=True goes through yams_graph_sgc_smooth_host instead of uploading here."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        assert x.ndim == 2
+        n, dim = x.shape
+        off = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+        c = np.ascontiguousarray(cols, dtype=np.uint32)
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        out = np.zeros((n, dim), np.float32)
+        if host_entry:
+            diag = _lib.SgcDiag()
+            self._check(self.L.yams_graph_sgc_smooth_host(self.ctx, x.ctypes.data, n, dim, off.ctypes.data, c.ctypes.data if c.size else None,
+                                                          w.ctypes.data if w.size else None, hops, out.ctypes.data, C.byref(diag)))
+            return out, diag.as_dict()
+        bufs = [self.to_device(a) if a.size else None for a in (x, off, c, w)]
+        d_out = self.alloc(x.size * 4 + 16)
+        try:
+            diag = self.sgc_smooth_device(*(b.ptr if b else None for b in bufs[:1]), n, dim, *(b.ptr if b else None for b in bufs[1:]),
+                                          hops, d_out.ptr)
+            if x.size:
+                out = d_out.download(np.float32, x.size).reshape(n, dim)
+        finally:
+            for b in bufs + [d_out]:
+                if b is not None:
+                    b.free()
+        return out, diag
+
     def scan_pq_topk(self, corpus: ScanCorpus, codes: np.ndarray, luts: np.ndarray, queries: np.ndarray, k: int, threshold: float = -1.0,
                      rerank_factor: int = 2, tie_keys: np.ndarray | None = None, row_of_index: np.ndarray | None = None,
                      candidates: np.ndarray | None = None, sum_lanes: int = 1, sum_flags: int | None = None) -> ScanResult:

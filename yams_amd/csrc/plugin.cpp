@@ -1,8 +1,8 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// eight interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
+// nine interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
+// semantic_graph_v1, topology_smooth_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
@@ -1055,6 +1055,17 @@ void sg_free_neighbors(void*, uint32_t* rows, float* sims, uint32_t* counts, flo
 
 yams_semantic_graph_v1 g_semantic_graph = {YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION, nullptr, GUARDED(sg_neighbors), GUARDED(sg_free_neighbors)};
 
+// ---- topology_smooth_v1: SGC smoothing over host memory (yams_graph_sgc_smooth_host) -----------------------------------------
+yams_status_t ts_smooth(void*, const float* rows, uint64_t n, uint32_t dim, const uint64_t* row_offsets, const uint32_t* cols,
+                        const float* weights, uint32_t hops, float* out, yams_sgc_diag_t* out_diag) {
+    NEED_INIT();
+    if (out_diag) std::memset(out_diag, 0, sizeof *out_diag);
+    Lease<yams_accel_ctx*> w(g.work_ctx);      // every check is the flat entry's: the caller owns every array
+    return yams_graph_sgc_smooth_host(w.v, rows, n, dim, row_offsets, cols, weights, hops, out, out_diag);
+}
+
+yams_topology_smooth_v1 g_topology_smooth = {YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION, nullptr, GUARDED(ts_smooth)};
+
 // ---- content_hash_v1 --------------------------------------------------------------------------
 // Every call leases one of the plugin's work contexts (own stream, own workspace), so hashing, chunking
 // and searches of different host threads overlap on the device instead of queueing on one mutex.
@@ -1554,6 +1565,7 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
         {YAMS_IFACE_VECTOR_ENTITY_SCAN_V1, YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION, &g_vector_entity_scan},
         {YAMS_IFACE_TOPOLOGY_CLUSTER_V1, YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION, &g_topology_cluster},
         {YAMS_IFACE_SEMANTIC_GRAPH_V1, YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION, &g_semantic_graph},
+        {YAMS_IFACE_TOPOLOGY_SMOOTH_V1, YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION, &g_topology_smooth},
         {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
         {YAMS_IFACE_CONTENT_CHECKSUM_V1, YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, &g_content_checksum},
         {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};
