@@ -789,6 +789,94 @@ YAMS_ACCEL_API yams_status_t yams_cluster_assign_device(
     const uint8_t* centroid_empty, uint32_t* out_assign, double* out_distance);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Cluster artifacts: centroids, routing representatives, the boundary spill's residuals      */
+/* ------------------------------------------------------------------------------------------ */
+/* After clustering every topology engine of the reference runs the same tail over the n x dim matrix
+ * (ConnectedComponentTopologyEngine, src/topology/topology_baseline.cpp:202-204,338; Louvain / KMeans through
+ * buildBatchFromAssignment, src/topology/topology_alternate_engines.cpp:218-220,263): detail::meanEmbedding
+ * (src/topology/topology_build_utils.h:27-56), selectDiverseRoutingRepresentatives and applyOrthogonalBoundarySpill
+ * (src/topology/topology_representatives.cpp:33-91, :93-287).  These entries are the array arithmetic of that tail; the shell
+ * that keeps the hash maps, the admission tests, the sorts and the member-list edits on the host, and probes which residual
+ * form the host's build has, is include/yams_accel/topology_artifacts.hpp.  The contract, restated:
+ *   centroid (h:27-56)  per dimension an fp32 running sum 0.0f + m0 + m1 + ... over the members IN THE ORDER OF THE MEMBER LIST
+ *             (the reference sorts members by document hash, alternate_engines.cpp:128-130: the order is an input, not the
+ *             k-means entry's ascending rows), then /= float(count), the IEEE divide.  No normalisation.  A cluster without
+ *             members has no centroid: out_counts = 0 and its row of out_centroids is zeros.
+ *   cosineDistance (cpp:13-29)  dot, lhsNorm, rhsNorm: three fp64 chains in element order (the product of two floats is exact
+ *             in fp64: fused or not, the same bits); 2.0 if either norm <= 0.0, else
+ *             1.0 - std::clamp(dot / (sqrt(l) * sqrt(r)), -1.0, 1.0) (std::clamp's comparisons: a NaN passes through).  A
+ *             row's norm is the same chain whoever asks: computed once per row.
+ *   selection (cpp:58-90)  candidates in the caller's order (the caller admits and sorts them); extraLimit = min(n_extra,
+ *             candidates); for selection s every unused candidate in list order gets d = distance(candidate, s == 0 ? centroid :
+ *             last selected) and minDist = std::min(minDist, d) (b < a ? b : a: a NaN d leaves it; minDist starts at DBL_MAX);
+ *             the first candidate with minDist > bestDistance STRICTLY wins (bestDistance starts at -1.0) and is used from
+ *             then on.  The centroid may be non-finite (an fp32 mean of +-FLT_MAX / 4 rows overflows): served as IEEE gives it.
+ *   residuals (cpp:119-141, :189-198, :235-252)  residual = double(e[d]) - double(c[d]); normSq += residual * residual;
+ *             residualDot += primaryResidual[d] * residual, with primaryResidual the same subtraction against the primary
+ *             centroid.  These products are NOT exact in fp64, so the bits depend on whether the host's compiler contracted
+ *             `x += a * b` into an fma (aarch64 with the default -ffp-contract does; x86-64 without -mfma does not):
+ *             YAMS_RESIDUAL_SEPARATE = a rounded multiply, then a rounded add; YAMS_RESIDUAL_FUSED = one fma per `+=`.
+ *             The shell probes which one the host's build is.
+ * Results equal the CPU loop bit for bit: no chain is split, no atomics.
+ * Lists are CSR: offsets [lists + 1] uint64 starting at 0 and never decreasing, entries uint32; fewer than 2^32 entries.
+ * Limits: n < 2^31, dim <= YAMS_CLUSTER_MAX_DIM, n_clusters <= YAMS_CLUSTER_MAX_K, n_extra <=
+ * YAMS_CLUSTER_MAX_REPRESENTATIVES, entries < 2^32: beyond, YAMS_ERR_UNSUPPORTED.  dim == 0, a null array that is needed,
+ * offsets that do not start at 0 or decrease, an entry out of range, an unknown form: YAMS_ERR_INVALID_ARG, and nothing is
+ * written.  n_clusters == 0 (centroids, representatives) or n == 0 (residuals): YAMS_OK, nothing written.
+ * Every call synchronises the context's stream before returning.  The _host twins take host arrays throughout. */
+#define YAMS_CLUSTER_MAX_REPRESENTATIVES 64u
+#define YAMS_RESIDUAL_SEPARATE 0u
+#define YAMS_RESIDUAL_FUSED 1u
+#define YAMS_CLUSTER_NONE 0xffffffffu
+/* meanEmbedding of every cluster.
+ *   rows             device [n][dim] fp32 (any values: served as IEEE gives them)
+ *   cluster_offsets  device [n_clusters + 1]        members  device: row indices < n, in the order of the sums
+ *   out_centroids    device [n_clusters][dim]       out_counts  device [n_clusters] uint32
+ * One chain per (cluster, dimension), one lane each: a wide cluster is parallel along dim, a skewed one is a long tail. */
+YAMS_ACCEL_API yams_status_t yams_cluster_centroids_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets, const uint32_t* members,
+    uint32_t n_clusters, float* out_centroids, uint32_t* out_counts);
+YAMS_ACCEL_API yams_status_t yams_cluster_centroids_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets, const uint32_t* members,
+    uint32_t n_clusters, float* out_centroids, uint32_t* out_counts);
+/* The selection loop of selectDiverseRoutingRepresentatives for every cluster at once.
+ *   candidates      device: row indices < n per cluster, in the order the caller gives (admitted, sorted by hash)
+ *   centroids       device [n_clusters][dim], raw       centroid_empty  device [n_clusters] uint8, nullable: a cluster whose
+ *                                                       flag is set selects nothing (cpp:37)
+ *   n_extra         routingRepresentativeCount - 1
+ *   out_selected    device [n_clusters][n_extra] uint32: POSITIONS in the cluster's candidate list, in selection order; unused
+ *                   slots hold YAMS_CLUSTER_NONE           out_counts  device [n_clusters]: the number selected
+ * A row (any row of the matrix) with a non-finite element: YAMS_ERR_INVALID_ARG (the admission test never sends one).
+ * Work: the selections are the dependent outer loop; each is one launch over ALL candidates of all clusters plus one
+ * reduction per cluster, all enqueued at once (no host round trip between selections). */
+YAMS_ACCEL_API yams_status_t yams_cluster_representatives_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets, const uint32_t* candidates,
+    const float* centroids, const uint8_t* centroid_empty, uint32_t n_clusters, uint32_t n_extra, uint32_t* out_selected,
+    uint32_t* out_counts);
+YAMS_ACCEL_API yams_status_t yams_cluster_representatives_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets, const uint32_t* candidates,
+    const float* centroids, const uint8_t* centroid_empty, uint32_t n_clusters, uint32_t n_extra, uint32_t* out_selected,
+    uint32_t* out_counts);
+/* The chains of applyOrthogonalBoundarySpill for (document, candidate cluster) pairs.
+ *   primary         device [n] uint32, nullable (= none anywhere): every document's primary cluster, YAMS_CLUSTER_NONE = none
+ *   cand_offsets, cand   device CSR over the documents: the candidate clusters of every document, in any order, repeats and
+ *                   the primary allowed; BOTH NULL = every cluster in index order (pair (u, c) at u * n_clusters + c)
+ *   form            YAMS_RESIDUAL_SEPARATE or YAMS_RESIDUAL_FUSED
+ *   out_primary_norm_sq  device [n] fp64: primaryNormSquared (0.0 for a document without a primary); needed with primary
+ *   out_cand_norm_sq     device [pairs] fp64: candidateNormSquared (the radius pass's radiusSquared is the same chain)
+ *   out_residual_dot     device [pairs] fp64: residualDot; needed with primary, undefined for a document without one
+ * Every input is served as IEEE gives it (the reference tests isfinite on the results).  The _host twin serves the documents in
+ * slices whose outputs occupy at most 256 MiB of device memory. */
+YAMS_ACCEL_API yams_status_t yams_cluster_residuals_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_clusters,
+    const uint32_t* primary, const uint64_t* cand_offsets, const uint32_t* cand, uint32_t form, double* out_primary_norm_sq,
+    double* out_cand_norm_sq, double* out_residual_dot);
+YAMS_ACCEL_API yams_status_t yams_cluster_residuals_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_clusters,
+    const uint32_t* primary, const uint64_t* cand_offsets, const uint32_t* cand, uint32_t form, double* out_primary_norm_sq,
+    double* out_cand_norm_sq, double* out_residual_dot);
+
+/* ------------------------------------------------------------------------------------------ */
 /* The semantic-neighbour graph: exact top-K self-join of the document-level embeddings         */
 /* ------------------------------------------------------------------------------------------ */
 /* EmbeddingService::updateSemanticNeighborGraphUnlocked (src/daemon/components/EmbeddingService.cpp) scores, for every
@@ -1348,6 +1436,32 @@ typedef struct yams_topology_smooth_v1 {
     yams_status_t (*smooth)(void* self, const float* rows, uint64_t n, uint32_t dim, const uint64_t* row_offsets, const uint32_t* cols,
                             const float* weights, uint32_t hops, float* out, yams_sgc_diag_t* out_diag);
 } yams_topology_smooth_v1;
+
+/* The cluster artifacts (yams_cluster_centroids_host / _representatives_host / _residuals_host) for a host that holds the
+ * embeddings in its own memory.  A separate interface, version 1, served by yams_plugin_get_interface and NOT listed in the
+ * manifest, for the reason given at vector_doc_scan_v1.  Host memory in, host memory out; the outputs are allocated by the
+ * plugin and released with the paired free_*.  Statuses and limits of the flat entries; an empty result gives null arrays. */
+#define YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1 "topology_artifacts_v1"
+#define YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1_VERSION 1u
+typedef struct yams_topology_artifacts_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1_VERSION */
+    void* self;
+    /* *out_centroids [n_clusters][dim], *out_counts [n_clusters] */
+    yams_status_t (*centroids)(void* self, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets,
+                               const uint32_t* members, uint32_t n_clusters, float** out_centroids, uint32_t** out_counts);
+    /* *out_selected [n_clusters][n_extra] (null when n_extra == 0), *out_counts [n_clusters] */
+    yams_status_t (*representatives)(void* self, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets,
+                                     const uint32_t* candidates, const float* centroids, const uint8_t* centroid_empty,
+                                     uint32_t n_clusters, uint32_t n_extra, uint32_t** out_selected, uint32_t** out_counts);
+    /* *out_cand_norm_sq [pairs]; with a primary also *out_primary_norm_sq [n] and *out_residual_dot [pairs] (without one both
+     * pointers may be null and come back null).  pairs = cand_offsets[n], or n * n_clusters without lists. */
+    yams_status_t (*residuals)(void* self, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_clusters,
+                               const uint32_t* primary, const uint64_t* cand_offsets, const uint32_t* cand, uint32_t form,
+                               double** out_primary_norm_sq, double** out_cand_norm_sq, double** out_residual_dot);
+    void (*free_centroids)(void* self, float* centroids, uint32_t* counts);
+    void (*free_representatives)(void* self, uint32_t* selected, uint32_t* counts);
+    void (*free_residuals)(void* self, double* primary_norm_sq, double* cand_norm_sq, double* residual_dot);
+} yams_topology_artifacts_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

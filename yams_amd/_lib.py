@@ -244,6 +244,27 @@ class TopologySmoothV1(C.Structure):  # topology_smooth_v1 (served by get_interf
 SGC_MAX_DIM, SGC_HUB_DEGREE = 4096, 512          # YAMS_SGC_MAX_DIM / _HUB_DEGREE
 
 
+f64p = C.POINTER(C.c_double)
+
+
+class TopologyArtifactsV1(C.Structure):  # topology_artifacts_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("centroids", C.CFUNCTYPE(ST, vp, f32p, C.c_uint64, C.c_uint32, u64p, u32p, C.c_uint32, C.POINTER(f32p), C.POINTER(u32p))),
+        ("representatives", C.CFUNCTYPE(ST, vp, f32p, C.c_uint64, C.c_uint32, u64p, u32p, f32p, u8p, C.c_uint32, C.c_uint32,
+                                        C.POINTER(u32p), C.POINTER(u32p))),
+        ("residuals", C.CFUNCTYPE(ST, vp, f32p, C.c_uint64, C.c_uint32, f32p, C.c_uint32, u32p, u64p, u32p, C.c_uint32,
+                                  C.POINTER(f64p), C.POINTER(f64p), C.POINTER(f64p))),
+        ("free_centroids", C.CFUNCTYPE(None, vp, f32p, u32p)),
+        ("free_representatives", C.CFUNCTYPE(None, vp, u32p, u32p)),
+        ("free_residuals", C.CFUNCTYPE(None, vp, f64p, f64p, f64p)),
+    ]
+
+
+CLUSTER_MAX_REPRESENTATIVES, CLUSTER_NONE = 64, 0xFFFFFFFF     # YAMS_CLUSTER_MAX_REPRESENTATIVES / YAMS_CLUSTER_NONE
+RESIDUAL_SEPARATE, RESIDUAL_FUSED = 0, 1                       # YAMS_RESIDUAL_*
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -313,6 +334,8 @@ EXPORTS = [
     "yams_cluster_kmeans_device", "yams_cluster_kmeans_host", "yams_cluster_assign_device",
     "yams_graph_semantic_neighbors_device", "yams_graph_semantic_neighbors_host",
     "yams_graph_sgc_smooth_device", "yams_graph_sgc_smooth_host",
+    "yams_cluster_centroids_device", "yams_cluster_centroids_host", "yams_cluster_representatives_device",
+    "yams_cluster_representatives_host", "yams_cluster_residuals_device", "yams_cluster_residuals_host",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -408,6 +431,12 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
                        C.POINTER(GraphDiag)]
     for fn in (L.yams_graph_sgc_smooth_device, L.yams_graph_sgc_smooth_host):
         fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, vp, C.POINTER(SgcDiag)]
+    for fn in (L.yams_cluster_centroids_device, L.yams_cluster_centroids_host):
+        fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp]
+    for fn in (L.yams_cluster_representatives_device, L.yams_cluster_representatives_host):
+        fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    for fn in (L.yams_cluster_residuals_device, L.yams_cluster_residuals_host):
+        fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

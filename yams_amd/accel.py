@@ -644,6 +644,119 @@ class Accel:
                     b.free()
         return out, diag
 
+    # ---- cluster artifacts (yams_cluster_centroids / _representatives / _residuals) ----------------------------------------
+    _GUARD = 0xA5
+
+    def _artifact_call(self, fn_device, fn_host, host_entry: bool, inputs: list, outputs: list, build_args, misalign: int = 0):
+        """Runs one artifact entry.  inputs: numpy arrays or None; outputs: (dtype, count) or None.  build_args(in_ptrs,
+        out_ptrs) gives the argument tuple after ctx.  Device outputs are followed by 64 guard bytes that must come back
+        untouched; misalign shifts every float input by that many bytes (float-aligned, not 16-byte-aligned bases)."""
+        sizes = [None if o is None else np.dtype(o[0]).itemsize * o[1] for o in outputs]
+        if host_entry:
+            outs = [None if nb is None else np.full(nb + 64, self._GUARD, np.uint8) for nb in sizes]
+            try:
+                self._check(fn_host(self.ctx, *build_args([None if a is None else a.ctypes.data for a in inputs],
+                                                          [None if o is None else o.ctypes.data for o in outs])))
+            except AccelError:
+                assert all(o is None or (o == self._GUARD).all() for o in outs), "a refused artifact call wrote to an output"
+                raise
+            assert all(o is None or (o[nb:] == self._GUARD).all() for o, nb in zip(outs, sizes)), "an artifact entry wrote behind its output"
+            return [None if o is None else o[:nb].view(outputs[i][0]).copy() for i, (o, nb) in enumerate(zip(outs, sizes))]
+        bufs, in_ptrs = [], []
+        try:
+            for a in inputs:
+                if a is None:
+                    in_ptrs.append(None)
+                    continue
+                shift = misalign if a.dtype == np.float32 else 0
+                b = self.alloc(a.nbytes + 32)
+                b.upload(a, shift)
+                bufs.append(b)
+                in_ptrs.append(b.ptr + shift)
+            out_bufs = []
+            for o in outputs:
+                if o is None:
+                    out_bufs.append(None)
+                    continue
+                nbytes = np.dtype(o[0]).itemsize * o[1]
+                b = self.alloc(nbytes + 64)
+                b.upload(np.full(nbytes + 64, self._GUARD, np.uint8))
+                bufs.append(b)
+                out_bufs.append(b)
+            try:
+                self._check(fn_device(self.ctx, *build_args(in_ptrs, [None if b is None else b.ptr for b in out_bufs])))
+            except AccelError:      # a refusal writes nothing: the outputs and the guard bytes behind them are as they were
+                for b in out_bufs:
+                    assert b is None or (b.download(np.uint8, b.nbytes) == self._GUARD).all(), "a refused artifact call wrote to an output"
+                raise
+            res = []
+            for o, b in zip(outputs, out_bufs):
+                if o is None:
+                    res.append(None)
+                    continue
+                nbytes = np.dtype(o[0]).itemsize * o[1]
+                raw = b.download(np.uint8, nbytes + 64)
+                assert (raw[nbytes:] == self._GUARD).all(), "an artifact entry wrote behind its output"
+                res.append(raw[:nbytes].view(o[0]).copy())
+            return res
+        finally:
+            for b in bufs:
+                b.free()
+
+    def cluster_centroids(self, rows: np.ndarray, cluster_offsets, members, host_entry: bool = False, misalign: int = 0):
+        """meanEmbedding of every cluster (yams_cluster_centroids_device / _host): rows [n][dim] float32, CSR member lists in
+        the order of the sums.  Returns (centroids [c][dim] float32, counts [c] uint32)."""
+        x = np.ascontiguousarray(rows, np.float32)
+        n, dim = x.shape
+        off = np.ascontiguousarray(cluster_offsets, np.uint64)
+        mem = np.ascontiguousarray(members, np.uint32)
+        c = len(off) - 1
+        cent, cnt = self._artifact_call(
+            self.L.yams_cluster_centroids_device, self.L.yams_cluster_centroids_host, host_entry,
+            [x if x.size else None, off, mem if mem.size else None], [(np.float32, c * dim), (np.uint32, c)],
+            lambda i, o: (i[0], n, dim, i[1], i[2], c, o[0], o[1]), misalign)
+        return cent.reshape(c, dim), cnt
+
+    def cluster_representatives(self, rows: np.ndarray, cluster_offsets, candidates, centroids: np.ndarray, n_extra: int,
+                                centroid_empty=None, host_entry: bool = False, misalign: int = 0):
+        """The selection loop of selectDiverseRoutingRepresentatives for every cluster (yams_cluster_representatives_device /
+        _host).  Returns (selected [c][n_extra] uint32 positions in the candidate lists, 0xffffffff = unused; counts [c])."""
+        x = np.ascontiguousarray(rows, np.float32)
+        n, dim = x.shape
+        off = np.ascontiguousarray(cluster_offsets, np.uint64)
+        cand = np.ascontiguousarray(candidates, np.uint32)
+        cen = np.ascontiguousarray(centroids, np.float32)
+        c = len(off) - 1
+        emp = None if centroid_empty is None else np.ascontiguousarray(centroid_empty, np.uint8)
+        sel, cnt = self._artifact_call(
+            self.L.yams_cluster_representatives_device, self.L.yams_cluster_representatives_host, host_entry,
+            [x if x.size else None, off, cand if cand.size else None, cen if cen.size else None, emp],
+            [(np.uint32, c * n_extra), (np.uint32, c)],
+            lambda i, o: (i[0], n, dim, i[1], i[2], i[3], i[4], c, n_extra, o[0], o[1]), misalign)
+        return sel.reshape(c, n_extra), cnt
+
+    def cluster_residuals(self, rows: np.ndarray, centroids: np.ndarray, primary=None, cand_offsets=None, cand=None,
+                          form: int = _lib.RESIDUAL_SEPARATE, host_entry: bool = False, misalign: int = 0):
+        """The chains of applyOrthogonalBoundarySpill (yams_cluster_residuals_device / _host).  primary [n] uint32 or None
+        (0xffffffff = none); cand_offsets / cand: CSR candidate lists, or None for every cluster in index order.  Returns
+        (primary_norm_sq [n] or None, cand_norm_sq [pairs], residual_dot [pairs] or None), float64."""
+        x = np.ascontiguousarray(rows, np.float32)
+        n, dim = x.shape
+        cen = np.ascontiguousarray(centroids, np.float32).reshape(-1, dim)
+        c = cen.shape[0]
+        pri = None if primary is None else np.ascontiguousarray(primary, np.uint32)
+        off = None if cand_offsets is None else np.ascontiguousarray(cand_offsets, np.uint64)
+        lst = None if cand is None else np.ascontiguousarray(cand, np.uint32)
+        pairs = int(off[-1]) if off is not None else n * c
+        if lst is not None and lst.size == 0:
+            lst = np.zeros(1, np.uint32)
+        pn, cn, rd = self._artifact_call(
+            self.L.yams_cluster_residuals_device, self.L.yams_cluster_residuals_host, host_entry,
+            [x if x.size else None, cen if cen.size else None, pri, off, lst],
+            [(np.float64, n) if pri is not None else None, (np.float64, pairs), (np.float64, pairs) if pri is not None else None],
+            lambda i, o: (i[0], n, dim, i[1], c, i[2], i[3], i[4], form, o[0], o[1], o[2]), misalign)
+        return pn, cn, rd
+
     def scan_pq_topk(self, corpus: ScanCorpus, codes: np.ndarray, luts: np.ndarray, queries: np.ndarray, k: int, threshold: float = -1.0,
                      rerank_factor: int = 2, tie_keys: np.ndarray | None = None, row_of_index: np.ndarray | None = None,
                      candidates: np.ndarray | None = None, sum_lanes: int = 1, sum_flags: int | None = None) -> ScanResult:

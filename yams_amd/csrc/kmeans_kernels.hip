@@ -25,6 +25,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "cosine_tail.h"
 #include "fp64_tile.h"
 #include "row_walk.h"
 
@@ -36,14 +37,7 @@ constexpr int kKmThreads = 256;
 constexpr int kKmMaxDim = 4096;          // YAMS_CLUSTER_MAX_DIM: one centroid fits the 16 KiB LDS stage of pick / centroid
 static_assert(kKmThreads == kRwRows && kKmThreads == kTileThreads, "the row walk and the tile are built for this workgroup");
 
-// cosineDistance's tail (:300-304) from the three sums; ra / rb = sqrt(na) / sqrt(nb).  std::clamp(v, lo, hi) is
-// (v < lo) ? lo : (hi < v) ? hi : v: a NaN passes through.
-__device__ __forceinline__ double km_distance(double dot, double na, double ra, double nb, double rb) {
-    if (na <= 0.0 || nb <= 0.0) return 2.0;
-    const double c = dot / (ra * rb);
-    const double cl = (c < -1.0) ? -1.0 : ((1.0 < c) ? 1.0 : c);
-    return 1.0 - cl;
-}
+// (cosineDistance's tail (:300-304), km_distance, is in cosine_tail.h)
 
 // normalized (:307-319) of the `dim` floats in v (LDS), written to out (global) and back to v; then (nb, sqrt(nb)) of the
 // result.  Both chains are one thread's, in element order.  Called by a whole workgroup.

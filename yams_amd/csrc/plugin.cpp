@@ -1,8 +1,8 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// nine interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, topology_smooth_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
+// ten interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
+// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
@@ -1066,6 +1066,86 @@ yams_status_t ts_smooth(void*, const float* rows, uint64_t n, uint32_t dim, cons
 
 yams_topology_smooth_v1 g_topology_smooth = {YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION, nullptr, GUARDED(ts_smooth)};
 
+// ---- topology_artifacts_v1: centroids, representatives, residuals over host memory (yams_cluster_*_host) -------------------
+// the limits bound the arrays allocated here; every other check is the flat entries'
+yams_status_t ta_centroids(void*, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets, const uint32_t* members,
+                           uint32_t n_clusters, float** out_centroids, uint32_t** out_counts) {
+    NEED_INIT();
+    if (!out_centroids || !out_counts) return YAMS_ERR_INVALID_ARG;
+    *out_centroids = nullptr; *out_counts = nullptr;
+    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM || n_clusters > YAMS_CLUSTER_MAX_K) return YAMS_ERR_UNSUPPORTED;
+    if (dim == 0) return YAMS_ERR_INVALID_ARG;
+    if (n_clusters == 0) return YAMS_OK;
+    auto* cent = static_cast<float*>(std::malloc(static_cast<size_t>(n_clusters) * dim * 4));
+    auto* cnt = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n_clusters) * 4));
+    if (!cent || !cnt) { std::free(cent); std::free(cnt); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    const yams_status_t st = yams_cluster_centroids_host(w.v, rows, n, dim, cluster_offsets, members, n_clusters, cent, cnt);
+    if (st != YAMS_OK) { std::free(cent); std::free(cnt); return st; }
+    *out_centroids = cent; *out_counts = cnt;
+    return YAMS_OK;
+}
+
+yams_status_t ta_representatives(void*, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets,
+                                 const uint32_t* candidates, const float* centroids, const uint8_t* centroid_empty, uint32_t n_clusters,
+                                 uint32_t n_extra, uint32_t** out_selected, uint32_t** out_counts) {
+    NEED_INIT();
+    if (!out_selected || !out_counts) return YAMS_ERR_INVALID_ARG;
+    *out_selected = nullptr; *out_counts = nullptr;
+    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM || n_clusters > YAMS_CLUSTER_MAX_K || n_extra > YAMS_CLUSTER_MAX_REPRESENTATIVES)
+        return YAMS_ERR_UNSUPPORTED;
+    if (dim == 0) return YAMS_ERR_INVALID_ARG;
+    if (n_clusters == 0) return YAMS_OK;
+    auto* sel = n_extra ? static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n_clusters) * n_extra * 4)) : nullptr;
+    auto* cnt = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n_clusters) * 4));
+    if ((n_extra && !sel) || !cnt) { std::free(sel); std::free(cnt); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    const yams_status_t st = yams_cluster_representatives_host(w.v, rows, n, dim, cluster_offsets, candidates, centroids, centroid_empty,
+                                                               n_clusters, n_extra, sel, cnt);
+    if (st != YAMS_OK) { std::free(sel); std::free(cnt); return st; }
+    *out_selected = sel; *out_counts = cnt;
+    return YAMS_OK;
+}
+
+yams_status_t ta_residuals(void*, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_clusters,
+                           const uint32_t* primary, const uint64_t* cand_offsets, const uint32_t* cand, uint32_t form,
+                           double** out_primary_norm_sq, double** out_cand_norm_sq, double** out_residual_dot) {
+    NEED_INIT();
+    if (!out_cand_norm_sq || (primary && (!out_primary_norm_sq || !out_residual_dot))) return YAMS_ERR_INVALID_ARG;
+    *out_cand_norm_sq = nullptr;
+    if (out_primary_norm_sq) *out_primary_norm_sq = nullptr;
+    if (out_residual_dot) *out_residual_dot = nullptr;
+    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM || n_clusters > YAMS_CLUSTER_MAX_K) return YAMS_ERR_UNSUPPORTED;
+    if (dim == 0 || (cand_offsets == nullptr) != (cand == nullptr)) return YAMS_ERR_INVALID_ARG;
+    if (n == 0) return YAMS_OK;
+    if (cand_offsets)      // the offsets size the arrays: judged here first
+        for (uint64_t i = 0; i < n; ++i)
+            if (cand_offsets[0] != 0 || cand_offsets[i + 1] < cand_offsets[i]) return YAMS_ERR_INVALID_ARG;
+    const uint64_t pairs = cand_offsets ? cand_offsets[n] : n * n_clusters;
+    const size_t p1 = static_cast<size_t>(pairs ? pairs : 1);
+    auto* cn = static_cast<double*>(std::malloc(p1 * 8));
+    auto* pn = primary ? static_cast<double*>(std::malloc(static_cast<size_t>(n) * 8)) : nullptr;
+    auto* rd = primary ? static_cast<double*>(std::malloc(p1 * 8)) : nullptr;
+    auto drop = [&] { std::free(cn); std::free(pn); std::free(rd); };
+    if (!cn || (primary && (!pn || !rd))) { drop(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    Lease<yams_accel_ctx*> w(g.work_ctx);
+    const yams_status_t st = yams_cluster_residuals_host(w.v, rows, n, dim, centroids, n_clusters, primary, cand_offsets, cand, form, pn, cn, rd);
+    if (st != YAMS_OK) { drop(); return st; }
+    *out_cand_norm_sq = cn;
+    if (primary) { *out_primary_norm_sq = pn; *out_residual_dot = rd; }
+    return YAMS_OK;
+}
+
+void ta_free_centroids(void*, float* centroids, uint32_t* counts) { std::free(centroids); std::free(counts); }
+void ta_free_representatives(void*, uint32_t* selected, uint32_t* counts) { std::free(selected); std::free(counts); }
+void ta_free_residuals(void*, double* primary_norm_sq, double* cand_norm_sq, double* residual_dot) {
+    std::free(primary_norm_sq); std::free(cand_norm_sq); std::free(residual_dot);
+}
+
+yams_topology_artifacts_v1 g_topology_artifacts = {YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1_VERSION, nullptr, GUARDED(ta_centroids),
+                                                   GUARDED(ta_representatives), GUARDED(ta_residuals), GUARDED(ta_free_centroids),
+                                                   GUARDED(ta_free_representatives), GUARDED(ta_free_residuals)};
+
 // ---- content_hash_v1 --------------------------------------------------------------------------
 // Every call leases one of the plugin's work contexts (own stream, own workspace), so hashing, chunking
 // and searches of different host threads overlap on the device instead of queueing on one mutex.
@@ -1566,6 +1646,7 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
         {YAMS_IFACE_TOPOLOGY_CLUSTER_V1, YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION, &g_topology_cluster},
         {YAMS_IFACE_SEMANTIC_GRAPH_V1, YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION, &g_semantic_graph},
         {YAMS_IFACE_TOPOLOGY_SMOOTH_V1, YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION, &g_topology_smooth},
+        {YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1, YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1_VERSION, &g_topology_artifacts},
         {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
         {YAMS_IFACE_CONTENT_CHECKSUM_V1, YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, &g_content_checksum},
         {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};
