@@ -67,7 +67,7 @@ enum yams_status_e {
 };
 #endif
 
-#define YAMS_ACCEL_VERSION_STRING "0.6.0" /* round 6: yams_scan_pq_topk_device, vector_scan_v1 v2 (pq_index_set / search_pq), yams_accel_trim, strict configuration */
+#define YAMS_ACCEL_VERSION_STRING "0.7.0" /* yams_route_index_* / yams_route_dense_*: the cluster router's dense signal over a resident index */
 
 /* ------------------------------------------------------------------------------------------ */
 /* Context                                                                                      */
@@ -877,6 +877,87 @@ YAMS_ACCEL_API yams_status_t yams_cluster_residuals_host(
     double* out_cand_norm_sq, double* out_residual_dot);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Cluster routing: the dense signal of SparseGuidedClusterRouter::route                        */
+/* ------------------------------------------------------------------------------------------ */
+/* The one consumer of the cluster artifacts on the query path is SparseGuidedClusterRouter::route
+ * (src/topology/topology_baseline.cpp:771-981; its index, buildRouteIndex, :700-769).  Its array arithmetic is the loop
+ * :873-920: per candidate cluster the query's cosine to the centroid and to each routing representative, mapped to [0, 1],
+ * maximum kept.  These entries are that loop over a RESIDENT table of cluster vectors (the reference caches its index per
+ * snapshot; so does the device).  The seed hash maps, the sparse mass, the ANN shortlist, the blend
+ * alpha * sparseNorm + (1 - alpha) * dense (a float expression the host's compiler may contract), the scoring modes, the
+ * sort and the cut stay on the host.  The contract, restated:
+ *   dotProduct (:669-678)  one fp64 chain over i = 0 .. dim-1, acc += double(a[i]) * double(b[i]), then float(acc).  The
+ *             products are exact in fp64, so fma equals `+=` bit for bit.
+ *   vectorNorm (:680-689)  the same kind of chain over v * v, then float(sqrt(acc)).
+ *   per vector  cos = dot_f32 / (qn_f32 * vn_f32) in float: one rounded multiply, one correctly rounded divide;
+ *             dense = std::clamp((cos + 1.0F) * 0.5F, 0.0F, 1.0F), clamp being (v < lo) ? lo : (hi < v) ? hi : v: a NaN
+ *             stays a NaN.  f32 denormals are kept.
+ *   centroid (:879-889)  evaluated only if qn > 0 && cn > 0 (false for a NaN norm); it ASSIGNS dense and sets observed.
+ *             Without it dense starts at 0.0F, unobserved.
+ *   representatives (:902-919)  positions 0 .. limit-1 of the reference's routingRepresentatives list, limit = the whole list
+ *             when maxRoutingRepresentatives == 0, else min(size, max - 1).  The limit counts POSITIONS IN THE REFERENCE'S
+ *             LIST, skipped ones included: every row carries its position.  A representative is skipped only if
+ *             qn <= 0 || rn <= 0 (or its size differs: such a vector is not in the table at all), so a NaN norm is NOT
+ *             skipped: it yields a NaN, which std::max(cur, NaN) = (cur < NaN) ? NaN : cur drops, while observed still
+ *             becomes true and the evaluation is still counted.  A NaN the centroid assigned survives every later
+ *             representative.  No -0.0f can arise after the map.
+ *   per call  every evaluation performed counts once (representativeDistanceEvaluations and
+ *             exactRepresentativeDistanceEvaluations both grow by out_evals[q]).  A cluster outside routeCandidates
+ *             (:844-871) is not scored: 0.0F, unobserved, not counted.  alpha >= 1 scores nothing: the shell does not call.
+ * Every output equals the reference's loop bit for bit (a NaN is some NaN).
+ * Limits: 1 <= dim <= YAMS_ROUTE_MAX_DIM, n_clusters <= YAMS_ROUTE_MAX_CLUSTERS, at most YAMS_ROUTE_MAX_REPRESENTATIVES
+ * representative rows per cluster, n_queries <= YAMS_ROUTE_MAX_QUERIES per call.  Outside them, or with a null array that is
+ * needed, offsets that do not start at 0, decrease or do not end at n_vectors, a centroid flag on an empty segment, or a
+ * representative position of 0xffff: YAMS_ERR_INVALID_ARG, and no output is written. */
+#define YAMS_ROUTE_MAX_DIM 4096u
+#define YAMS_ROUTE_MAX_CLUSTERS 65536u
+#define YAMS_ROUTE_MAX_REPRESENTATIVES 64u
+#define YAMS_ROUTE_MAX_QUERIES 1024u
+typedef struct yams_route_index yams_route_index;
+typedef struct yams_route_index_info_t {
+    uint64_t n_vectors;
+    uint32_t n_clusters;
+    uint32_t dim;
+    uint64_t bytes;          /* device memory the index holds */
+} yams_route_index_info_t;
+typedef struct yams_route_diag_t {
+    uint64_t pairs;          /* (query, row) pairs the score kernels covered */
+    uint32_t slices;         /* launches of the score kernel (a call is served in slices of queries) */
+    uint32_t form;           /* the last slice's kernel: 0 = one lane per row (up to 8 queries), 1 = the fp64 tile */
+} yams_route_diag_t;
+/* Builds the resident index: copies the table to the device and computes every row's norm.
+ *   vectors          [n_vectors][dim] fp32, cluster after cluster; inside a cluster the centroid first (when it has one), then
+ *                    the representatives the host admits (those of the index dimension), in any order
+ *   cluster_offsets  [n_clusters + 1] uint32: the rows of cluster c are [off[c], off[c + 1])
+ *   has_centroid     [n_clusters] uint8: nonzero = the first row of the segment is the centroid
+ *   position         [n_vectors] uint16: a representative row's place in the reference's list (ignored for a centroid row)
+ *   out_norms        [n_vectors] fp32, nullable: float(sqrt(chain)) per row — centroidNorms / routingRepresentativeNorms
+ * _device: every array is device memory.  _host: every array is host memory.  The index belongs to `ctx` and is used on its
+ * stream; destroy it before the context. */
+YAMS_ACCEL_API yams_status_t yams_route_index_create_device(
+    yams_accel_ctx* ctx, const float* vectors, uint64_t n_vectors, uint32_t dim, const uint32_t* cluster_offsets,
+    const uint8_t* has_centroid, const uint16_t* position, uint32_t n_clusters, yams_route_index** out_index, float* out_norms);
+YAMS_ACCEL_API yams_status_t yams_route_index_create_host(
+    yams_accel_ctx* ctx, const float* vectors, uint64_t n_vectors, uint32_t dim, const uint32_t* cluster_offsets,
+    const uint8_t* has_centroid, const uint16_t* position, uint32_t n_clusters, yams_route_index** out_index, float* out_norms);
+YAMS_ACCEL_API void yams_route_index_destroy(yams_route_index* index);
+YAMS_ACCEL_API yams_status_t yams_route_index_info(const yams_route_index* index, yams_route_index_info_t* out_info);
+/* The dense signal of n_queries queries against the index.
+ *   queries       [n_queries][dim] fp32 (any values)
+ *   rep_limit     maxRoutingRepresentatives: 0 = every position, else positions < rep_limit - 1
+ *   candidates    nullable (= every cluster): bitset [n_queries][ceil(n_clusters / 32)] uint32, bit c % 32 of word c / 32
+ *   out_dense     [n_queries][n_clusters] fp32      out_observed  [n_queries][n_clusters] uint8 (0 / 1)
+ *   out_evals     [n_queries] uint32: evaluations performed       diag  nullable (host memory in both forms)
+ * n_queries == 0: YAMS_OK, nothing written.  _host serves the queries in slices whose outputs occupy at most 256 MiB of device
+ * memory.  Synchronises the context's stream before returning. */
+YAMS_ACCEL_API yams_status_t yams_route_dense_device(
+    yams_route_index* index, const float* queries, uint32_t n_queries, uint32_t rep_limit, const uint32_t* candidates,
+    float* out_dense, uint8_t* out_observed, uint32_t* out_evals, yams_route_diag_t* diag);
+YAMS_ACCEL_API yams_status_t yams_route_dense_host(
+    yams_route_index* index, const float* queries, uint32_t n_queries, uint32_t rep_limit, const uint32_t* candidates,
+    float* out_dense, uint8_t* out_observed, uint32_t* out_evals, yams_route_diag_t* diag);
+
+/* ------------------------------------------------------------------------------------------ */
 /* The semantic-neighbour graph: exact top-K self-join of the document-level embeddings         */
 /* ------------------------------------------------------------------------------------------ */
 /* EmbeddingService::updateSemanticNeighborGraphUnlocked (src/daemon/components/EmbeddingService.cpp) scores, for every
@@ -1462,6 +1543,28 @@ typedef struct yams_topology_artifacts_v1 {
     void (*free_representatives)(void* self, uint32_t* selected, uint32_t* counts);
     void (*free_residuals)(void* self, double* primary_norm_sq, double* cand_norm_sq, double* residual_dot);
 } yams_topology_artifacts_v1;
+
+/* The cluster router's dense signal (yams_route_index_create_host / yams_route_dense_host) for a host that holds the cluster
+ * vectors in its own memory.  A separate interface, version 1, served by yams_plugin_get_interface and NOT listed in the
+ * manifest, for the reason given at vector_doc_scan_v1.  Host memory in, host memory out: every output is the caller's array.
+ * An index lives on the device under an id until index_destroy (or the plugin's shutdown); calls on one index take turns,
+ * calls on different indexes overlap.  Statuses and limits of the flat entries; an unknown id: YAMS_ERR_NOT_FOUND. */
+#define YAMS_IFACE_TOPOLOGY_ROUTE_V1 "topology_route_v1"
+#define YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION 1u
+typedef struct yams_topology_route_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION */
+    void* self;
+    /* out_norms: the caller's [n_vectors], nullable */
+    yams_status_t (*index_create)(void* self, const float* vectors, uint64_t n_vectors, uint32_t dim, const uint32_t* cluster_offsets,
+                                  const uint8_t* has_centroid, const uint16_t* position, uint32_t n_clusters, uint64_t* out_id,
+                                  float* out_norms);
+    yams_status_t (*index_info)(void* self, uint64_t id, yams_route_index_info_t* out_info);
+    /* out_dense / out_observed: the caller's [n_queries][n_clusters]; out_evals: [n_queries]; out_diag nullable */
+    yams_status_t (*dense)(void* self, uint64_t id, const float* queries, uint32_t n_queries, uint32_t rep_limit,
+                           const uint32_t* candidates, float* out_dense, uint8_t* out_observed, uint32_t* out_evals,
+                           yams_route_diag_t* out_diag);
+    yams_status_t (*index_destroy)(void* self, uint64_t id);
+} yams_topology_route_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

@@ -265,6 +265,24 @@ CLUSTER_MAX_REPRESENTATIVES, CLUSTER_NONE = 64, 0xFFFFFFFF     # YAMS_CLUSTER_MA
 RESIDUAL_SEPARATE, RESIDUAL_FUSED = 0, 1                       # YAMS_RESIDUAL_*
 
 
+class TopologyRouteV1(C.Structure):  # topology_route_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("index_create", C.CFUNCTYPE(C.c_int, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, u64p, vp)),
+        ("index_info", C.CFUNCTYPE(C.c_int, vp, C.c_uint64, vp)),
+        ("dense", C.CFUNCTYPE(C.c_int, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp)),
+        ("index_destroy", C.CFUNCTYPE(C.c_int, vp, C.c_uint64)),
+    ]
+
+
+class RouteIndexInfo(C.Structure):  # yams_route_index_info_t
+    _fields_ = [("n_vectors", C.c_uint64), ("n_clusters", C.c_uint32), ("dim", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class RouteDiag(C.Structure):  # yams_route_diag_t
+    _fields_ = [("pairs", C.c_uint64), ("slices", C.c_uint32), ("form", C.c_uint32)]
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -336,6 +354,8 @@ EXPORTS = [
     "yams_graph_sgc_smooth_device", "yams_graph_sgc_smooth_host",
     "yams_cluster_centroids_device", "yams_cluster_centroids_host", "yams_cluster_representatives_device",
     "yams_cluster_representatives_host", "yams_cluster_residuals_device", "yams_cluster_residuals_host",
+    "yams_route_index_create_device", "yams_route_index_create_host", "yams_route_index_destroy", "yams_route_index_info",
+    "yams_route_dense_device", "yams_route_dense_host",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -437,6 +457,13 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
         fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     for fn in (L.yams_cluster_residuals_device, L.yams_cluster_residuals_host):
         fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    for fn in (L.yams_route_index_create_device, L.yams_route_index_create_host):
+        fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(vp), vp]
+    L.yams_route_index_destroy.argtypes = [vp]
+    L.yams_route_index_destroy.restype = None
+    L.yams_route_index_info.argtypes = [vp, C.POINTER(RouteIndexInfo)]
+    for fn in (L.yams_route_dense_device, L.yams_route_dense_host):
+        fn.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(RouteDiag)]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

@@ -120,6 +120,52 @@ class DedupSet:
         return nn.value, bn.value, bd.value
 
 
+def pack_candidates(mask: np.ndarray) -> np.ndarray:
+    """bool [q][c] -> the bitset yams_route_dense takes: uint32 [q][ceil(c / 32)], bit c % 32 of word c / 32."""
+    m = np.asarray(mask, bool)
+    q, c = m.shape
+    words = (c + 31) // 32
+    padded = np.zeros((q, words * 32), np.uint8)
+    padded[:, :c] = m
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little").view("<u4").reshape(q, words))
+
+
+class RouteIndex:
+    """Owns a yams_route_index (the resident table of cluster vectors of one topology snapshot)."""
+
+    def __init__(self, acc: "Accel", vectors, cluster_offsets, has_centroid, position, host_entry: bool = False, misalign: int = 0):
+        x = np.ascontiguousarray(vectors, np.float32)
+        assert x.ndim == 2
+        self.acc, self.h = acc, None
+        v, self.dim = x.shape
+        off = np.ascontiguousarray(cluster_offsets, np.uint32)
+        has = np.ascontiguousarray(has_centroid, np.uint8)
+        pos = np.ascontiguousarray(position, np.uint16)
+        self.n_clusters, self.n_vectors = len(off) - 1, v
+        h = C.c_void_p()
+        (norms,) = acc._artifact_call(
+            acc.L.yams_route_index_create_device, acc.L.yams_route_index_create_host, host_entry,
+            [x if x.size else None, off, has if has.size else None, pos if pos.size else None], [(np.float32, v)],
+            lambda i, o: (i[0], v, self.dim, i[1], i[2], i[3], self.n_clusters, C.byref(h), o[0]), misalign)
+        self.h, self.norms = h, norms
+
+    def info(self) -> dict:
+        inf = _lib.RouteIndexInfo()
+        self.acc._check(self.acc.L.yams_route_index_info(self.h, C.byref(inf)))
+        return {"n_vectors": inf.n_vectors, "n_clusters": inf.n_clusters, "dim": inf.dim, "bytes": inf.bytes}
+
+    def close(self):
+        if self.h and getattr(self.acc, "ctx", None):      # (the index uses its context: see DedupSet.close)
+            self.acc.L.yams_route_index_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ShardedScan:
     """yams_scan_sharded_*: one search over a corpus row-sharded across several devices behind the C ABI — one
     process, one RCCL communicator over the shard devices, all-gather + merge per batch, `lanes` batches in
@@ -647,15 +693,17 @@ class Accel:
     # ---- cluster artifacts (yams_cluster_centroids / _representatives / _residuals) ----------------------------------------
     _GUARD = 0xA5
 
-    def _artifact_call(self, fn_device, fn_host, host_entry: bool, inputs: list, outputs: list, build_args, misalign: int = 0):
+    def _artifact_call(self, fn_device, fn_host, host_entry: bool, inputs: list, outputs: list, build_args, misalign: int = 0, ctx=None):
         """Runs one artifact entry.  inputs: numpy arrays or None; outputs: (dtype, count) or None.  build_args(in_ptrs,
         out_ptrs) gives the argument tuple after ctx.  Device outputs are followed by 64 guard bytes that must come back
-        untouched; misalign shifts every float input by that many bytes (float-aligned, not 16-byte-aligned bases)."""
+        untouched; misalign shifts every float input by that many bytes (float-aligned, not 16-byte-aligned bases).  ctx: the
+        handle the entry takes first, when it is not the context."""
+        ctx = self.ctx if ctx is None else ctx
         sizes = [None if o is None else np.dtype(o[0]).itemsize * o[1] for o in outputs]
         if host_entry:
             outs = [None if nb is None else np.full(nb + 64, self._GUARD, np.uint8) for nb in sizes]
             try:
-                self._check(fn_host(self.ctx, *build_args([None if a is None else a.ctypes.data for a in inputs],
+                self._check(fn_host(ctx, *build_args([None if a is None else a.ctypes.data for a in inputs],
                                                           [None if o is None else o.ctypes.data for o in outs])))
             except AccelError:
                 assert all(o is None or (o == self._GUARD).all() for o in outs), "a refused artifact call wrote to an output"
@@ -684,7 +732,7 @@ class Accel:
                 bufs.append(b)
                 out_bufs.append(b)
             try:
-                self._check(fn_device(self.ctx, *build_args(in_ptrs, [None if b is None else b.ptr for b in out_bufs])))
+                self._check(fn_device(ctx, *build_args(in_ptrs, [None if b is None else b.ptr for b in out_bufs])))
             except AccelError:      # a refusal writes nothing: the outputs and the guard bytes behind them are as they were
                 for b in out_bufs:
                     assert b is None or (b.download(np.uint8, b.nbytes) == self._GUARD).all(), "a refused artifact call wrote to an output"
@@ -756,6 +804,31 @@ class Accel:
             [(np.float64, n) if pri is not None else None, (np.float64, pairs), (np.float64, pairs) if pri is not None else None],
             lambda i, o: (i[0], n, dim, i[1], c, i[2], i[3], i[4], form, o[0], o[1], o[2]), misalign)
         return pn, cn, rd
+
+    # ---- cluster routing (yams_route_index_* / yams_route_dense_*) ----------------------------------------------------------
+    def route_index(self, vectors: np.ndarray, cluster_offsets, has_centroid, position, host_entry: bool = False,
+                    misalign: int = 0) -> "RouteIndex":
+        """The resident table of cluster vectors (yams_route_index_create_device / _host): vectors [v][dim] float32, cluster
+        after cluster, the centroid first where has_centroid says so; position [v] uint16 = a representative's place in the
+        reference's list.  The row norms come back as `.norms`."""
+        return RouteIndex(self, vectors, cluster_offsets, has_centroid, position, host_entry, misalign)
+
+    def route_dense(self, index: "RouteIndex", queries: np.ndarray, rep_limit: int = 0, candidates=None, host_entry: bool = False,
+                    misalign: int = 0):
+        """The dense signal of every query against the index (yams_route_dense_device / _host).  candidates: None or a bool
+        array [q][c].  Returns (dense [q][c] float32, observed [q][c] bool, evaluations [q] uint32, diag dict)."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, index.dim)
+        nq, c = q.shape[0], index.n_clusters
+        bits = None
+        if candidates is not None:
+            bits = pack_candidates(np.asarray(candidates, bool).reshape(nq, c))
+        diag = _lib.RouteDiag()
+        dense, obs, ev = self._artifact_call(
+            self.L.yams_route_dense_device, self.L.yams_route_dense_host, host_entry,
+            [q if q.size else None, bits if bits is not None and bits.size else None],
+            [(np.float32, nq * c), (np.uint8, nq * c), (np.uint32, nq)],
+            lambda i, o: (i[0], nq, rep_limit, i[1], o[0], o[1], o[2], C.byref(diag)), misalign, ctx=index.h)
+        return dense.reshape(nq, c), obs.reshape(nq, c).astype(bool), ev, {"pairs": diag.pairs, "slices": diag.slices, "form": diag.form}
 
     def scan_pq_topk(self, corpus: ScanCorpus, codes: np.ndarray, luts: np.ndarray, queries: np.ndarray, k: int, threshold: float = -1.0,
                      rerank_factor: int = 2, tie_keys: np.ndarray | None = None, row_of_index: np.ndarray | None = None,

@@ -2,7 +2,7 @@
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
 // ten interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
+// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
@@ -1371,6 +1371,74 @@ yams_content_hash_v1 g_content_hash = {YAMS_IFACE_CONTENT_HASH_V1_VERSION, nullp
                                        GUARDED(ch_verify_many), GUARDED(ch_dedup_create), GUARDED(ch_dedup_insert),
                                        GUARDED(ch_dedup_contains), GUARDED(ch_dedup_size), GUARDED(ch_dedup_destroy)};
 
+// ---- topology_route_v1: the cluster router's dense signal over a resident index (yams_route_index_* / yams_route_dense_host) ----
+// Route indexes: each owns a context (its table lives in that context's device memory, its calls use that context's workspace)
+// and a mutex — the shape of the dedup sets above.
+struct RouteEntry { yams_accel_ctx* ctx = nullptr; yams_route_index* index = nullptr; std::mutex mu; };
+std::mutex g_route_mu;
+std::map<uint64_t, std::shared_ptr<RouteEntry>> g_route;
+uint64_t g_next_route = 1;
+
+void destroy_route(RouteEntry& e) {
+    if (e.index) yams_route_index_destroy(e.index);
+    if (e.ctx) yams_accel_ctx_destroy(e.ctx);
+    e.index = nullptr; e.ctx = nullptr;
+}
+std::shared_ptr<RouteEntry> find_route(uint64_t id) {
+    std::lock_guard<std::mutex> lk(g_route_mu);
+    auto it = g_route.find(id);
+    return it == g_route.end() ? nullptr : it->second;
+}
+
+yams_status_t tr_index_create(void*, const float* vectors, uint64_t n_vectors, uint32_t dim, const uint32_t* cluster_offsets,
+                              const uint8_t* has_centroid, const uint16_t* position, uint32_t n_clusters, uint64_t* out_id, float* out_norms) {
+    NEED_INIT();
+    if (!out_id) return YAMS_ERR_INVALID_ARG;
+    auto e = std::make_shared<RouteEntry>();
+    yams_status_t st = yams_accel_ctx_create(g.devices[0], nullptr, &e->ctx);
+    if (st != YAMS_OK) return st;
+    st = yams_route_index_create_host(e->ctx, vectors, n_vectors, dim, cluster_offsets, has_centroid, position, n_clusters, &e->index, out_norms);
+    if (st != YAMS_OK) { destroy_route(*e); return st; }
+    std::lock_guard<std::mutex> lk(g_route_mu);
+    *out_id = g_next_route++;
+    g_route[*out_id] = e;
+    return YAMS_OK;
+}
+yams_status_t tr_index_info(void*, uint64_t id, yams_route_index_info_t* out_info) {
+    NEED_INIT();
+    auto e = find_route(id);
+    if (!e) return YAMS_ERR_NOT_FOUND;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->index) return YAMS_ERR_NOT_FOUND;
+    return yams_route_index_info(e->index, out_info);
+}
+yams_status_t tr_dense(void*, uint64_t id, const float* queries, uint32_t n_queries, uint32_t rep_limit, const uint32_t* candidates,
+                       float* out_dense, uint8_t* out_observed, uint32_t* out_evals, yams_route_diag_t* out_diag) {
+    NEED_INIT();
+    auto e = find_route(id);
+    if (!e) return YAMS_ERR_NOT_FOUND;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->index) return YAMS_ERR_NOT_FOUND;
+    return yams_route_dense_host(e->index, queries, n_queries, rep_limit, candidates, out_dense, out_observed, out_evals, out_diag);
+}
+yams_status_t tr_index_destroy(void*, uint64_t id) {
+    NEED_INIT();
+    std::shared_ptr<RouteEntry> e;
+    {
+        std::lock_guard<std::mutex> lk(g_route_mu);
+        auto it = g_route.find(id);
+        if (it == g_route.end()) return YAMS_ERR_NOT_FOUND;
+        e = it->second;
+        g_route.erase(it);
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    destroy_route(*e);
+    return YAMS_OK;
+}
+
+yams_topology_route_v1 g_topology_route = {YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION, nullptr, GUARDED(tr_index_create), GUARDED(tr_index_info),
+                                           GUARDED(tr_dense), GUARDED(tr_index_destroy)};
+
 // ---- content_checksum_v1: the compressed store's CRC-32 over host memory (yams_crc32_many_host) ------------------------------
 yams_status_t cs_crc32_many(void*, const uint8_t* const* msgs, const size_t* lens, size_t n, uint32_t* out) {
     NEED_INIT();
@@ -1519,6 +1587,11 @@ void teardown_locked() { // g.mu held exclusively
         for (auto& kv : g_dedup) { std::lock_guard<std::mutex> el(kv.second->mu); destroy_dedup(*kv.second); }
         g_dedup.clear();
     }
+    {
+        std::lock_guard<std::mutex> lk(g_route_mu);
+        for (auto& kv : g_route) { std::lock_guard<std::mutex> el(kv.second->mu); destroy_route(*kv.second); }
+        g_route.clear();
+    }
     if (g.sharded) yams_scan_sharded_destroy(g.sharded);
     g.sharded = nullptr;
     for (auto* c : g.work_ctx.drain()) yams_accel_ctx_destroy(c);
@@ -1647,6 +1720,7 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
         {YAMS_IFACE_SEMANTIC_GRAPH_V1, YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION, &g_semantic_graph},
         {YAMS_IFACE_TOPOLOGY_SMOOTH_V1, YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION, &g_topology_smooth},
         {YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1, YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1_VERSION, &g_topology_artifacts},
+        {YAMS_IFACE_TOPOLOGY_ROUTE_V1, YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION, &g_topology_route},
         {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
         {YAMS_IFACE_CONTENT_CHECKSUM_V1, YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, &g_content_checksum},
         {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};
