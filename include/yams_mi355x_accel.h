@@ -958,6 +958,61 @@ YAMS_ACCEL_API yams_status_t yams_route_dense_host(
     float* out_dense, uint8_t* out_observed, uint32_t* out_evals, yams_route_diag_t* diag);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Topological quality: H0 persistence of a point cloud (computePersistenceH0)                  */
+/* ------------------------------------------------------------------------------------------ */
+/* After every rebuild TopologyManager (src/daemon/components/TopologyManager.cpp:660-707) hands the mean embeddings of the
+ * clusters with at least two members — what yams_cluster_centroids_device returns — to yams::search::computePersistenceH0
+ * (src/search/topological_quality.cpp:75-128): m (m - 1) / 2 pairwise distances, a stable sort, a percentile, Kruskal.  This
+ * entry is that function; the shell around it is include/yams_accel/topological_quality.hpp.  deterministicSubsample
+ * (:150-167) stays the host's: std::shuffle's sequence belongs to its standard library.  The contract, restated:
+ *   points     m rows of `dim` floats: rows[select[0]], rows[select[1]], ... in the order given (repeats allowed: duplicate
+ *              points are legal input), or the rows 0 .. n-1 without `select`.  m < 2: value 0.0.  E = m (m - 1) / 2.
+ *   distance (:51-61)  for i < j: acc = 0.0; per k in element order d = double(a[k]) - double(b[k]); acc += d * d;
+ *              dist = sqrt(acc), correctly rounded.  d carries up to 53 bits, so d * d is NOT exact and the bits of `acc += d * d`
+ *              depend on whether the host's compiler contracted it into an fma: YAMS_RESIDUAL_SEPARATE = a rounded multiply,
+ *              then a rounded add; YAMS_RESIDUAL_FUSED = one fma.  The shell probes which one the host's build is.
+ *              (-d)^2 == d^2 bit for bit: the matrix is symmetric; acc starts at +0.0 and adds non-negatives: never -0.0.
+ *   norm (:63-71, :102)  the order statistic of the E distances at idx = size_t(std::clamp(0.95 * double(E - 1), 0.0,
+ *              double(E - 1))), computed on the host with exactly that expression.  norm <= 0: value 0.0.
+ *   merges (:97-126)  Kruskal over the edges ascending, at most m - 2 merges, total += dist / norm per merge (the divide and
+ *              the sum run on the host, in ascending order).  The sorted weights of ANY minimum spanning tree equal
+ *              Kruskal's (for every t the number of tree edges <= t is m minus the components of the graph of edges <= t), so
+ *              the reference's stable sort does not have to be reproduced; the heaviest tree edge is the one left out.
+ *              m == 2: no merge, value 0.0 (norm and the one distance are still reported).
+ * Every output equals the reference's computation bit for bit in the form asked for.
+ * Limits, decided before anything is allocated: m > YAMS_QUALITY_MAX_POINTS (an m x m fp64 matrix of 2 GiB), dim >
+ * YAMS_CLUSTER_MAX_DIM, n >= 2^31: YAMS_ERR_UNSUPPORTED.  dim == 0, a null array that is needed (out; rows when m > 0), an
+ * unknown form, a select entry >= n, a non-finite element of a selected row (inf - inf would put NaNs into a sort the
+ * reference leaves undefined; judged at every m >= 1): YAMS_ERR_INVALID_ARG.  The m x m matrix comes from the context's
+ * workspace (or is out_distances itself in the _device form); when it cannot be had: YAMS_ERR_RESOURCE_EXHAUSTED.  After any
+ * status but YAMS_OK nothing has been written to any output.
+ *   rows               [n][dim] fp32
+ *   select, n_select   nullable: n_select uint32 row indices < n; NULL = all n rows (n_select is ignored).  This is how a caller
+ *                      drops the clusters with fewer than two members from a centroid matrix already on the device.
+ *   form               YAMS_RESIDUAL_SEPARATE or YAMS_RESIDUAL_FUSED
+ *   out                host memory in both forms
+ *   out_distances      nullable [m][m] fp64: the matrix, diagonal +0.0
+ *   out_merge_weights  nullable [m - 1] fp64: the tree's edge weights ascending (the first m - 2 are the merges)
+ *   out_stage_ms       nullable, host memory in both forms: [3] = pair distances, order statistic, spanning tree (device time)
+ * _device: rows, select, out_distances, out_merge_weights are device memory.  _host: host memory; only the selected rows
+ * travel.  Synchronises the context's stream before returning. */
+#define YAMS_QUALITY_MAX_POINTS 16384u
+typedef struct yams_persistence_h0_t {
+    double value;            /* computePersistenceH0's return value */
+    double norm;             /* the 95th-percentile distance (0.0 when m < 2) */
+    uint64_t norm_index;     /* its index among the sorted distances */
+    uint64_t n_edges;        /* m (m - 1) / 2 */
+    uint32_t n_points;       /* m */
+    uint32_t n_merges;       /* merges summed into value: m - 2, or 0 when m < 2 or norm <= 0 */
+} yams_persistence_h0_t;
+YAMS_ACCEL_API yams_status_t yams_quality_persistence_h0_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select, uint32_t form,
+    yams_persistence_h0_t* out, double* out_distances, double* out_merge_weights, float* out_stage_ms);
+YAMS_ACCEL_API yams_status_t yams_quality_persistence_h0_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select, uint32_t form,
+    yams_persistence_h0_t* out, double* out_distances, double* out_merge_weights, float* out_stage_ms);
+
+/* ------------------------------------------------------------------------------------------ */
 /* The semantic-neighbour graph: exact top-K self-join of the document-level embeddings         */
 /* ------------------------------------------------------------------------------------------ */
 /* EmbeddingService::updateSemanticNeighborGraphUnlocked (src/daemon/components/EmbeddingService.cpp) scores, for every
@@ -1565,6 +1620,22 @@ typedef struct yams_topology_route_v1 {
                            yams_route_diag_t* out_diag);
     yams_status_t (*index_destroy)(void* self, uint64_t id);
 } yams_topology_route_v1;
+
+/* computePersistenceH0 (yams_quality_persistence_h0_host) for a host that holds the point cloud in its own memory.  A separate
+ * interface, version 1, served by yams_plugin_get_interface and NOT listed in the manifest, for the reason given at
+ * vector_doc_scan_v1.  Host memory in, host memory out; the two arrays are allocated by the plugin when asked for (a non-null
+ * pointer to receive them) and released with free_persistence_h0.  Statuses and limits of the flat entry; m < 2 gives a null
+ * *out_merge_weights. */
+#define YAMS_IFACE_TOPOLOGY_QUALITY_V1 "topology_quality_v1"
+#define YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION 1u
+typedef struct yams_topology_quality_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION */
+    void* self;
+    /* out_distances / out_merge_weights: nullable; *out_distances [m][m], *out_merge_weights [m - 1] */
+    yams_status_t (*persistence_h0)(void* self, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select,
+                                    uint32_t form, yams_persistence_h0_t* out, double** out_distances, double** out_merge_weights);
+    void (*free_persistence_h0)(void* self, double* distances, double* merge_weights);
+} yams_topology_quality_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

@@ -283,6 +283,23 @@ class RouteDiag(C.Structure):  # yams_route_diag_t
     _fields_ = [("pairs", C.c_uint64), ("slices", C.c_uint32), ("form", C.c_uint32)]
 
 
+class PersistenceH0(C.Structure):  # yams_persistence_h0_t
+    _fields_ = [("value", C.c_double), ("norm", C.c_double), ("norm_index", C.c_uint64), ("n_edges", C.c_uint64),
+                ("n_points", C.c_uint32), ("n_merges", C.c_uint32)]
+
+
+QUALITY_MAX_POINTS = 16384                                     # YAMS_QUALITY_MAX_POINTS
+
+
+class TopologyQualityV1(C.Structure):  # topology_quality_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("persistence_h0", C.CFUNCTYPE(C.c_int, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.POINTER(PersistenceH0),
+                                       C.POINTER(f64p), C.POINTER(f64p))),
+        ("free_persistence_h0", C.CFUNCTYPE(None, vp, f64p, f64p)),
+    ]
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -356,6 +373,7 @@ EXPORTS = [
     "yams_cluster_representatives_host", "yams_cluster_residuals_device", "yams_cluster_residuals_host",
     "yams_route_index_create_device", "yams_route_index_create_host", "yams_route_index_destroy", "yams_route_index_info",
     "yams_route_dense_device", "yams_route_dense_host",
+    "yams_quality_persistence_h0_device", "yams_quality_persistence_h0_host",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -464,6 +482,8 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
     L.yams_route_index_info.argtypes = [vp, C.POINTER(RouteIndexInfo)]
     for fn in (L.yams_route_dense_device, L.yams_route_dense_host):
         fn.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(RouteDiag)]
+    for fn in (L.yams_quality_persistence_h0_device, L.yams_quality_persistence_h0_host):
+        fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.POINTER(PersistenceH0), vp, vp, vp]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

@@ -805,6 +805,30 @@ class Accel:
             lambda i, o: (i[0], n, dim, i[1], c, i[2], i[3], i[4], form, o[0], o[1], o[2]), misalign)
         return pn, cn, rd
 
+    # ---- topological quality (yams_quality_persistence_h0_*) --------------------------------------------------------------
+    def persistence_h0(self, rows: np.ndarray, select=None, form: int = _lib.RESIDUAL_SEPARATE, host_entry: bool = False,
+                       want_distances: bool = False, want_weights: bool = False, misalign: int = 0):
+        """computePersistenceH0 of the points rows[select] (all rows without select): yams_quality_persistence_h0_device /
+        _host.  Returns a dict: value, norm, norm_index, n_edges, n_points, n_merges and, when asked for, distances [m][m]
+        float64, weights [m - 1] float64 ascending."""
+        x = np.ascontiguousarray(rows, np.float32)
+        n, dim = x.shape
+        sel = None if select is None else np.ascontiguousarray(select, np.uint32)
+        m = n if sel is None else len(sel)
+        res = _lib.PersistenceH0()
+        if sel is not None and sel.size == 0:
+            sel = np.zeros(1, np.uint32)
+        dist, w = self._artifact_call(
+            self.L.yams_quality_persistence_h0_device, self.L.yams_quality_persistence_h0_host, host_entry,
+            [x if x.size else None, sel], [(np.float64, m * m) if want_distances else None, (np.float64, max(m - 1, 0)) if want_weights else None],
+            lambda i, o: (i[0], n, dim, i[1], m, form, C.byref(res), o[0], o[1], None), misalign)
+        out = {k: getattr(res, k) for k, _ in _lib.PersistenceH0._fields_}
+        if want_distances:
+            out["distances"] = dist.reshape(m, m)
+        if want_weights:
+            out["weights"] = w
+        return out
+
     # ---- cluster routing (yams_route_index_* / yams_route_dense_*) ----------------------------------------------------------
     def route_index(self, vectors: np.ndarray, cluster_offsets, has_centroid, position, host_entry: bool = False,
                     misalign: int = 0) -> "RouteIndex":

@@ -1,8 +1,8 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// ten interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
+// twelve interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
+// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, topology_quality_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
@@ -1439,6 +1439,35 @@ yams_status_t tr_index_destroy(void*, uint64_t id) {
 yams_topology_route_v1 g_topology_route = {YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION, nullptr, GUARDED(tr_index_create), GUARDED(tr_index_info),
                                            GUARDED(tr_dense), GUARDED(tr_index_destroy)};
 
+// ---- topology_quality_v1: computePersistenceH0 over host memory (yams_quality_persistence_h0_host) --------------------------
+// the limits bound the arrays allocated here; every other check is the flat entry's
+yams_status_t tq_persistence_h0(void*, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select,
+                                uint32_t form, yams_persistence_h0_t* out, double** out_distances, double** out_merge_weights) {
+    NEED_INIT();
+    if (!out) return YAMS_ERR_INVALID_ARG;
+    const uint64_t m = select ? n_select : n;
+    if (m > YAMS_QUALITY_MAX_POINTS || dim > YAMS_CLUSTER_MAX_DIM || n >= (1ull << 31)) return YAMS_ERR_UNSUPPORTED;
+    double* dist = nullptr; double* w = nullptr;
+    if (out_distances && m) dist = static_cast<double*>(std::malloc(static_cast<size_t>(m) * m * 8));
+    if (out_merge_weights && m >= 2) w = static_cast<double*>(std::malloc(static_cast<size_t>(m - 1) * 8));
+    if ((out_distances && m && !dist) || (out_merge_weights && m >= 2 && !w)) { std::free(dist); std::free(w); return YAMS_ERR_RESOURCE_EXHAUSTED; }
+    yams_persistence_h0_t res{};
+    yams_status_t st;
+    {
+        Lease<yams_accel_ctx*> lease(g.work_ctx);
+        st = yams_quality_persistence_h0_host(lease.v, rows, n, dim, select, n_select, form, &res, dist, w, nullptr);
+    }
+    if (st != YAMS_OK) { std::free(dist); std::free(w); return st; }
+    *out = res;
+    if (out_distances) *out_distances = dist;
+    if (out_merge_weights) *out_merge_weights = w;
+    return YAMS_OK;
+}
+void tq_free_persistence_h0(void*, double* distances, double* merge_weights) { std::free(distances); std::free(merge_weights); }
+
+yams_topology_quality_v1 g_topology_quality = {YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION, nullptr, GUARDED(tq_persistence_h0),
+                                               GUARDED(tq_free_persistence_h0)};
+
 // ---- content_checksum_v1: the compressed store's CRC-32 over host memory (yams_crc32_many_host) ------------------------------
 yams_status_t cs_crc32_many(void*, const uint8_t* const* msgs, const size_t* lens, size_t n, uint32_t* out) {
     NEED_INIT();
@@ -1721,6 +1750,7 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
         {YAMS_IFACE_TOPOLOGY_SMOOTH_V1, YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION, &g_topology_smooth},
         {YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1, YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1_VERSION, &g_topology_artifacts},
         {YAMS_IFACE_TOPOLOGY_ROUTE_V1, YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION, &g_topology_route},
+        {YAMS_IFACE_TOPOLOGY_QUALITY_V1, YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION, &g_topology_quality},
         {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
         {YAMS_IFACE_CONTENT_CHECKSUM_V1, YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, &g_content_checksum},
         {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};
