@@ -1,5 +1,6 @@
 // accel_ctx.cpp — context lifecycle, workspace, timing, memory helpers of the C ABI.
 #include "accel_ctx.h"
+#include "xcd_deal.h"
 
 #include <algorithm>
 #include <array>
@@ -118,6 +119,7 @@ yams_status_t ws_get(yams_accel_ctx* ctx, const char* name, size_t bytes, void**
     if (b.cap < bytes) {
         if (b.p) {
             YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (b.p == ctx->xcd_deal.table) ctx->xcd_deal.table = nullptr; // (what lived in it across calls starts again)
             YA_HIP(ctx, hipFree(b.p));
             b.p = nullptr; b.cap = 0;
         }
@@ -144,6 +146,7 @@ size_t ws_trim(yams_accel_ctx* ctx, size_t keep_bytes) {
         if (!synced) { (void)hipStreamSynchronize(ctx->stream); synced = true; }
         if (hipFree(b.p) != hipSuccess) (void)hipGetLastError();
         freed += b.cap;
+        if (b.p == ctx->xcd_deal.table) ctx->xcd_deal.table = nullptr;
         b.p = nullptr; b.cap = 0;
     }
     return freed;
@@ -461,6 +464,18 @@ yams_status_t yams_accel_device_info_json(yams_accel_ctx* ctx, char** out_json) 
         os << ",\"last_host_ingest\":{\"bytes\":" << hi.bytes << ",\"batches\":" << hi.batches << ",\"batch_bytes\":" << hi.batch_bytes
            << ",\"slots\":" << hi.slots << ",\"alloc_ms\":" << hi.alloc_ms
            << ",\"release_ms\":" << hi.release_ms << ",\"total_ms\":" << hi.total_ms << "}";
+    if (ctx->xcd_deal.table) { // the int8 sweep's current deal of units to the XCDs (weights relative to an equal share, off[] of the filter launch)
+        uint32_t t[yams_accel::XCD_TABLE_TICKS];
+        YA_HIP(ctx, hipMemcpyAsync(t, ctx->xcd_deal.table, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+        YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        os << ",\"xcd_deal\":{\"streams_per_xcd\":" << ctx->xcd_deal.streams_x << ",\"units\":" << ctx->xcd_deal.n_units_filter << ",\"weights\":[";
+        for (uint32_t x = 0; x < 8; ++x) os << (x ? "," : "") << t[yams_accel::XCD_TABLE_WEIGHTS + x] / 65536.0;
+        os << "],\"off\":[";
+        for (uint32_t x = 0; x <= 8; ++x) os << (x ? "," : "") << t[yams_accel::XCD_TABLE_OFF_FILTER + x];
+        os << "],\"off_sample\":[";
+        for (uint32_t x = 0; x <= 8; ++x) os << (x ? "," : "") << t[yams_accel::XCD_TABLE_OFF_SAMPLE + x];
+        os << "]}";
+    }
     os << "}";
     const std::string s = os.str();
     char* buf = static_cast<char*>(std::malloc(s.size() + 1));

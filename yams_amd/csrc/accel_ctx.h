@@ -64,6 +64,11 @@ struct yams_accel_ctx {
     struct HostIngestStats { double alloc_ms = 0, release_ms = 0, total_ms = 0; uint64_t batch_bytes = 0, bytes = 0; uint32_t batches = 0, slots = 0; } host_ingest;
     // last ingest result (device arrays live in bufs)
     yams_ingest_result_t ingest{};
+    // the int8 sweep's deal of units to the XCDs (xcd_deal.h): which plan the running weights in `table` (workspace "i8_xcd")
+    // belong to.  A batch on another corpus view, dim, metric or query-tile count — or after the workspace moved — starts
+    // from equal weights again.
+    struct XcdDealState { const void* rows_i8 = nullptr; uint64_t n_rows = 0; uint32_t dim = 0, n_qt = 0, streams_x = 0, n_units_filter = 0,
+                          n_units_sample = 0, l2 = 0, forced = 0; uint32_t* table = nullptr; } xcd_deal;
 };
 
 namespace yams_accel {

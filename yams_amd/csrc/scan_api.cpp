@@ -617,9 +617,41 @@ yams_status_t run_filter(Batch& b, Filter& f, bool* done) {
         const size_t z_cnt = (static_cast<size_t>(regions) * 4 + 255) & ~size_t(255), z_over = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
         unsigned char* zeroed;
         YA_TRY(ws_get(ctx, "i8_zeroed", z_cnt + z_over + static_cast<size_t>(sync_words) * 4, (void**)&zeroed));
+        // the deal of the resident-query sweep's units to the XCDs (xcd_deal.h): the table outlives the call — running weights,
+        // the end ticks of this context's previous filter launch — and the same launch that prepares the queries turns it into
+        // this batch's unit ranges.  A plan the weights were not learnt on starts from equal weights.
+        XcdDealPrep deal{};
+        uint64_t deal_words = 0;
+        if (i8_xcd_deal_plan(L, &deal, &deal_words)) {
+            YA_TRY(ws_get(ctx, "i8_xcd", static_cast<size_t>(deal_words) * 4, (void**)&L.i8_xcd));
+            auto& k = ctx->xcd_deal;
+            const bool same = k.table == L.i8_xcd && k.rows_i8 == corpus->rows_i8 && k.n_rows == corpus->n_rows && k.dim == b.dim && k.n_qt == deal.n_qt &&
+                              k.streams_x == deal.streams_x && k.n_units_filter == deal.n_units_filter && k.n_units_sample == deal.n_units_sample &&
+                              k.l2 == (L.i8_l2 ? 1u : 0u) && !k.forced;
+            deal.table = L.i8_xcd;
+            deal.mode = same ? XCD_DEAL_FEEDBACK : XCD_DEAL_RESET;
+            k.table = L.i8_xcd; k.rows_i8 = corpus->rows_i8; k.n_rows = corpus->n_rows; k.dim = b.dim; k.n_qt = deal.n_qt; k.streams_x = deal.streams_x;
+            k.n_units_filter = deal.n_units_filter; k.n_units_sample = deal.n_units_sample; k.l2 = L.i8_l2 ? 1u : 0u; k.forced = 0;
+#ifdef YAMS_ACCEL_MEASURE
+            // YAMS_ACCEL_XCD_WEIGHTS=w0,...,w7 (relative to an equal share) forces the weights, =equal keeps the equal deal (A/B runs, the tests)
+            if (const char* wv = std::getenv("YAMS_ACCEL_XCD_WEIGHTS")) {
+                deal.mode = XCD_DEAL_FORCED;
+                for (int x = 0; x < 8; ++x) deal.forced[x] = XCD_DEAL_ONE;
+                const char* p = wv;
+                for (int x = 0; x < 8 && *p; ++x) {
+                    char* end = nullptr;
+                    const double v = std::strtod(p, &end);
+                    if (end == p) break;
+                    deal.forced[x] = static_cast<uint32_t>(std::min(std::max(v, 0.0), 16.0) * XCD_DEAL_ONE + 0.5);
+                    p = *end == ',' ? end + 1 : end;
+                }
+                k.forced = 1; // (feedback starts afresh once the knob is gone)
+            }
+#endif
+        }
         // (cleared by the query preparation of the int8 tier: one launch where there were a fill and a launch)
         YA_HIP(ctx, launch_prep_i8(st, b.d_qprep, nq, L.q_pad, b.dim, const_cast<int8_t*>(L.q_i8), const_cast<float*>(L.q_meta), L.i8_l2,
-                                   reinterpret_cast<uint32_t*>(zeroed), (z_cnt + z_over) / 4 + sync_words, (corpus->i8_flags & YAMS_SCAN_I8_ROTATED) != 0));
+                                   reinterpret_cast<uint32_t*>(zeroed), (z_cnt + z_over) / 4 + sync_words, (corpus->i8_flags & YAMS_SCAN_I8_ROTATED) != 0, &deal));
         L.log_cnt = reinterpret_cast<uint32_t*>(zeroed);
         L.q_over = f.d_qover = reinterpret_cast<uint32_t*>(zeroed + z_cnt);
         if (sync_words) L.i8_sync = reinterpret_cast<uint32_t*>(zeroed + z_cnt + z_over);
@@ -645,11 +677,20 @@ yams_status_t run_filter(Batch& b, Filter& f, bool* done) {
       gs.leave(); }
     if (i8) YA_HIP(ctx, launch_i8_log_gather(st, L));
 #ifdef YAMS_ACCEL_MEASURE
-    if (i8 && L.i8_sync) if (const char* dump = std::getenv("YAMS_ACCEL_DUMP_SYNC")) { // per-wave begin / end ticks of the resident-query kernel
+    if (!(i8 && L.i8_sync)) {}
+    else if (const char* dump = std::getenv("YAMS_ACCEL_DUMP_SYNC")) { // per-wave begin / end ticks of the resident-query kernel
         std::vector<uint32_t> h(i8_sync_words(L));
         YA_HIP(ctx, hipMemcpyAsync(h.data(), L.i8_sync, h.size() * 4, hipMemcpyDeviceToHost, st));
         YA_HIP(ctx, hipStreamSynchronize(st));
         if (FILE* fp = std::fopen(dump, "wb")) { std::fwrite(h.data(), 4, h.size(), fp); std::fclose(fp); }
+    } else if (const char* log = std::getenv("YAMS_ACCEL_DUMP_SYNC_LOG")) { // the same, one record per launch APPENDED (several lanes, several launches:
+        // scripts/dbg/xcd_balance.py): {magic, context, words, n_streams} + the table, one unbuffered write per record
+        std::vector<uint32_t> h(4 + i8_sync_words(L));
+        YA_HIP(ctx, hipMemcpyAsync(h.data() + 4, L.i8_sync, (h.size() - 4) * 4, hipMemcpyDeviceToHost, st));
+        YA_HIP(ctx, hipStreamSynchronize(st));
+        h[0] = 0x58434442u; h[1] = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(ctx)); h[2] = static_cast<uint32_t>(h.size() - 4);
+        h[3] = static_cast<uint32_t>(i8_sync_words(L) / (12u * 32u * 2u));
+        if (FILE* fp = std::fopen(log, "ab")) { std::setvbuf(fp, nullptr, _IONBF, 0); std::fwrite(h.data(), 4, h.size(), fp); std::fclose(fp); }
     }
     const int bv = f.bf16_version;
     if (bv != 2 && bv != 3 && bv != 4 && bv != 20 && bv != 30 && bv != 40 && bv != 50 && bv != 70 && bv != 80 && !(bv >= 81 && bv <= 99)) { // ablated kernels produce no candidates: stop here

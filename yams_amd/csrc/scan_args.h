@@ -23,6 +23,8 @@ struct ScanArgs {
     uint32_t log_cap;
     uint32_t* q_over;          // [n_queries] set when a log region was too small for a query's survivors
     uint32_t* i8_sync;         // resident-query form: [n_streams][4 wave pairs][32 query tiles] strips drawn so far (zeroed before the launch)
+    const uint32_t* xcd_off;   // resident-query form: off[0..8], the unit range of every XCD in this launch (xcd_deal.h; written by prep_i8_kernel)
+    uint32_t* xcd_ticks;       // filter launch: [workgroup][9] = {begin, end of waves 0..7} in wall_clock64 ticks, what the next batch's deal learns from; nullable
     // int8 tier, L2 batches (scan_i8_kernel.hip, "L2 on the int8 tier"): the per-row part of the integer threshold
     const uint8_t* i8_row_bias; // [ceil(n_rows / 64)][4 lq][4 rb][4 r] a_r of row 16 rb + 4 lq + r of the block; null for cosine
     const uint32_t* i8_q_bias;  // [q_pad] m_q: a survivor needs I >= T(block, q) + a_r m_q

@@ -23,11 +23,13 @@
 // first k-slabs are still on their way from HBM), so after the k loop "survives" is a sign bit: the
 // epilogue is one v_max3 tree per query block, and only lanes that hold a survivor (~1 %) look at
 // single elements.
+#include <climits>
 #include <cstdlib>
 #include <type_traits>
 
 #include "lds_dma.h"
 #include "scan_args.h"
+#include "xcd_deal.h"
 
 namespace yams_accel {
 
@@ -579,9 +581,13 @@ __global__ __launch_bounds__(R_THREADS, 1) void scan_tiles_i8r_kernel(ScanArgs a
     const uint32_t bid = blockIdx.x;
     const uint32_t xcd = bid & 7u, slot = bid >> 3;       // workgroup b runs on XCD b % 8
     const uint32_t qt = slot % n_qt, st = slot / n_qt;    // the query tile it holds, its row stream on this XCD
-    if (st >= (n_streams >> 3)) return;
+    const uint32_t streams_x = n_streams >> 3;
+    if (st >= streams_x) return;
     const uint32_t stream = st * 8u + xcd;
-    if (stream >= n_units) return;
+    // this XCD's range of units (xcd_deal.h); whatever the table holds, no unit lies past the launch's last
+    const uint32_t off_lo = a.xcd_off[xcd], off_hi = a.xcd_off[xcd + 1u] < n_units ? a.xcd_off[xcd + 1u] : n_units;
+    if (xcd_deal_unit(off_lo, off_hi, streams_x, st, 0u) >= n_units) return;
+    if (!SAMPLE && a.xcd_ticks && threadIdx.x == 0) a.xcd_ticks[(stream * n_qt + qt) * XCD_TICKS_PER_WG] = static_cast<uint32_t>(wall_clock64()) | 1u; // (0 = not written)
 
 #ifdef YAMS_ACCEL_MEASURE
     const uint64_t t_begin = wall_clock64();
@@ -612,7 +618,7 @@ __global__ __launch_bounds__(R_THREADS, 1) void scan_tiles_i8r_kernel(ScanArgs a
     const uint32_t piece_row_stride = static_cast<uint32_t>(nslab) * 1024u; // bytes between the pieces of consecutive 16-row blocks
     // Strip k of this wave's PAIR (waves w and w + 4 share a SIMD and a strip sequence, see "work sharing"
     // below): unit (k >> 1) of the stream, tile (k & 1) of that unit, rows [64 (w & 3), +64) of the tile.
-    auto unit_of = [&](uint32_t k) __attribute__((always_inline)) -> uint32_t { return stream + (k >> 1) * n_streams; };
+    auto unit_of = [&](uint32_t k) __attribute__((always_inline)) -> uint32_t { return xcd_deal_unit(off_lo, off_hi, streams_x, st, k >> 1); }; // (0xffffffff past the stream's end)
     auto locate = [&](uint32_t k, Geo& g) __attribute__((always_inline)) {
         const uint32_t un_ = unit_of(k);
         const uint32_t sel = un_ < n_units ? 2u * un_ + (k & 1u) : 0xffffffffu;
@@ -1098,6 +1104,9 @@ __global__ __launch_bounds__(R_THREADS, 1) void scan_tiles_i8r_kernel(ScanArgs a
     if (ZL) zs_flush();
     // (the lane id is derived again: holding it over the launch cost the direct form its 256th register and a scratch slot)
     if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u && ABL == 0 && !SAMPLE) a.log_cnt[log_region] = log_pos < a.log_cap ? log_pos : a.log_cap;
+    // when this wave ended: the next batch's deal of units to the XCDs learns from it (prep_i8_kernel)
+    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u && !SAMPLE && a.xcd_ticks)
+        a.xcd_ticks[(stream * n_qt + qt) * XCD_TICKS_PER_WG + 1u + static_cast<uint32_t>(wid)] = static_cast<uint32_t>(wall_clock64()) | 1u;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the ring's last (unused) pieces must land before the LDS is handed back
 #ifdef YAMS_ACCEL_MEASURE
     if (lane == 0 && n_qt <= 8) { // measurement build: when each wave started and ended (100 MHz ticks) and how many strips it took
@@ -1502,10 +1511,65 @@ __global__ __launch_bounds__(256) void i8_meta_stats_kernel(const float* meta, u
 // rot_p != 0: the corpus' shadow is in the ROTATED layout (shadow_build_i8_kernel): the query goes through the same map first
 // (one workgroup, the Walsh-Hadamard stages through LDS), and its slop takes the distance between the computed and the exact
 // rotations of row and query (1e-5 of the query's norm: see the bound above wave_fwht).
+// The deal of the sweep's units to the XCDs for this batch (xcd_deal.h), by ONE workgroup of prep_i8_kernel: the end ticks the
+// previous filter launch of this context left in the table -> the time every XCD took -> the running weights -> off[] of this
+// batch's filter launch and of its sample pass.  The ticks are cleared behind the reading: a launch that did not write all of
+// them (another kernel form, an aborted call) teaches nothing.  Ticks are the low 32 bits of a 100 MHz counter (they wrap
+// every 43 s): all times are signed differences to one of them.
+__device__ __forceinline__ void xcd_deal_update(const XcdDealPrep& d) {
+    __shared__ int s_end[XCD_DEAL_XCDS];
+    __shared__ int s_begin;
+    __shared__ uint32_t s_missing, s_ref;
+    uint32_t* const w = d.table + XCD_TABLE_WEIGHTS;
+    uint32_t* const off_f = d.table + XCD_TABLE_OFF_FILTER;
+    uint32_t* const ticks = d.table + XCD_TABLE_TICKS;
+    const uint32_t n_wg = d.streams_x * XCD_DEAL_XCDS * d.n_qt;
+    if (threadIdx.x < XCD_DEAL_XCDS) s_end[threadIdx.x] = INT_MIN;
+    if (threadIdx.x == 0) { s_begin = INT_MAX; s_missing = 0u; s_ref = 0u; }
+    __syncthreads();
+    if (d.mode == XCD_DEAL_FEEDBACK)
+        for (uint32_t g = threadIdx.x; g < n_wg; g += blockDim.x) atomicMax(&s_ref, ticks[g * XCD_TICKS_PER_WG]);
+    __syncthreads();
+    if (d.mode == XCD_DEAL_FEEDBACK) {
+        const uint32_t ref = s_ref; // any begin tick that was written
+        for (uint32_t g = threadIdx.x; g < n_wg; g += blockDim.x) {
+            const uint32_t stream = g / d.n_qt, x = stream & 7u, st = stream >> 3;
+            if (xcd_deal_stream_length(off_f[x], off_f[x + 1u], d.streams_x, st) == 0u) continue; // (the previous deal: this batch's is written below)
+            const uint32_t b = ticks[g * XCD_TICKS_PER_WG];
+            if (b == 0u) { atomicOr(&s_missing, 1u); continue; }
+            atomicMin(&s_begin, static_cast<int>(b - ref));
+            for (uint32_t wv = 0; wv < 8u; ++wv) {
+                const uint32_t e = ticks[g * XCD_TICKS_PER_WG + 1u + wv];
+                if (e == 0u) atomicOr(&s_missing, 1u); else atomicMax(&s_end[x], static_cast<int>(e - ref));
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_wg * XCD_TICKS_PER_WG; i += blockDim.x) ticks[i] = 0u;
+    if (threadIdx.x != 0) return;
+    uint32_t wl[XCD_DEAL_XCDS], off[XCD_DEAL_XCDS + 1];
+    for (uint32_t x = 0; x < XCD_DEAL_XCDS; ++x) wl[x] = d.mode == XCD_DEAL_FEEDBACK ? w[x] : (d.mode == XCD_DEAL_FORCED ? d.forced[x] : XCD_DEAL_ONE);
+    if (d.mode == XCD_DEAL_FEEDBACK && s_missing == 0u && s_begin != INT_MAX) {
+        uint32_t n[XCD_DEAL_XCDS];
+        int64_t t[XCD_DEAL_XCDS];
+        for (uint32_t x = 0; x < XCD_DEAL_XCDS; ++x) {
+            n[x] = off_f[x + 1u] - off_f[x];
+            t[x] = s_end[x] == INT_MIN ? 0 : static_cast<int64_t>(s_end[x]) - s_begin;
+        }
+        xcd_deal_feedback(wl, n, t);
+    }
+    for (uint32_t x = 0; x < XCD_DEAL_XCDS; ++x) w[x] = wl[x];
+    xcd_deal_offsets(wl, d.n_units_filter, d.streams_x, off);
+    for (uint32_t x = 0; x <= XCD_DEAL_XCDS; ++x) off_f[x] = off[x];
+    xcd_deal_offsets(wl, d.n_units_sample, d.streams_x, off);
+    for (uint32_t x = 0; x <= XCD_DEAL_XCDS; ++x) d.table[XCD_TABLE_OFF_SAMPLE + x] = off[x];
+}
+
 __global__ __launch_bounds__(256) void prep_i8_kernel(const float* qprep, uint32_t nq, uint32_t q_pad, uint32_t dim,
                                                       int8_t* q_i8, float* q_meta, int raw, uint32_t* zero_words, uint32_t n_zero_words,
-                                                      uint32_t rot_p, float rot_scale) {
+                                                      uint32_t rot_p, float rot_scale, XcdDealPrep deal) {
     const uint32_t q = blockIdx.x;
+    if (deal.table && q == gridDim.x - 1u) xcd_deal_update(deal); // (a padding query's workgroup when the batch has any: it has the least to do)
     // the filter launch's zero-initialised tables (log region counts, overflow marks, strip counters: scan_api.cpp "i8_zeroed")
     for (uint32_t i = q * 256u + threadIdx.x; i < n_zero_words; i += gridDim.x * 256u) zero_words[i] = 0u;
     __shared__ float red[256];
@@ -1824,13 +1888,15 @@ hipError_t launch_shadow_build_i8(hipStream_t st, const float* rows, uint64_t fi
 }
 
 hipError_t launch_prep_i8(hipStream_t st, const float* qprep, uint32_t nq, uint32_t q_pad, uint32_t dim,
-                          int8_t* q_i8, float* q_meta, bool raw_queries, uint32_t* zero_words, uint64_t n_zero_words, bool rotated) {
+                          int8_t* q_i8, float* q_meta, bool raw_queries, uint32_t* zero_words, uint64_t n_zero_words, bool rotated, const XcdDealPrep* deal) {
     if (q_pad == 0) return hipSuccess;
+    XcdDealPrep xd{};
+    if (deal && deal->table) xd = *deal;
     if (n_zero_words >> 32) return hipErrorInvalidValue;
     const uint32_t p = rotated ? i8_rotation_window(dim) : 0;
     if (rotated && !p) return hipErrorInvalidValue;
     hipLaunchKernelGGL(prep_i8_kernel, dim3(q_pad), dim3(256), p ? static_cast<size_t>(dim) * 4 : 0, st, qprep, nq, q_pad, dim, q_i8, q_meta, raw_queries ? 1 : 0,
-                       zero_words, zero_words ? static_cast<uint32_t>(n_zero_words) : 0u, p, p ? i8_rotation_scale(p) : 0.f);
+                       zero_words, zero_words ? static_cast<uint32_t>(n_zero_words) : 0u, p, p ? i8_rotation_scale(p) : 0.f, xd);
     return hipGetLastError();
 }
 
@@ -1955,6 +2021,17 @@ hipError_t launch_i8_collect_sample(hipStream_t st, const ScanLaunch& L) {
     return hipGetLastError();
 }
 
+bool i8_xcd_deal_plan(const ScanLaunch& L, XcdDealPrep* p, uint64_t* table_words) {
+    const ResidentPlan r = i8_resident_plan(L);
+    if (!r.use) return false;
+    p->n_units_filter = r.n_units;
+    p->n_units_sample = (L.plan.n_sample_tiles + 1u) / 2u;
+    p->streams_x = r.n_streams / XCD_DEAL_XCDS;
+    p->n_qt = r.n_qt;
+    *table_words = XCD_TABLE_TICKS + static_cast<uint64_t>(r.n_streams) * r.n_qt * XCD_TICKS_PER_WG;
+    return true;
+}
+
 uint64_t i8_sync_words(const ScanLaunch& L) {
     const ResidentPlan r = i8_resident_plan(L);
     // [n_streams][4 pairs][32] strip counters (+ [n_streams][8][32] for the measurement build's timestamps), twice: the
@@ -2057,6 +2134,11 @@ hipError_t launch_scan_i8(hipStream_t st, const ScanLaunch& L, int mode, int ver
     if (a.n_sel_tiles == 0) return hipSuccess;
     const uint32_t hgrid = ((2u * a.n_sel_tiles + 7) / 8) * a.n_qtiles * 8;
     const ResidentPlan rp = i8_resident_plan(L);
+    if (rp.use && !L.i8_xcd) return hipErrorInvalidValue; // the resident-query forms read their unit ranges from the deal's table
+    if (rp.use) { // (the sample pass shares the weights and has its own off[]; only the filter launch leaves end ticks)
+        a.xcd_off = L.i8_xcd + (mode == MODE_SAMPLE ? XCD_TABLE_OFF_SAMPLE : XCD_TABLE_OFF_FILTER);
+        a.xcd_ticks = mode == MODE_SAMPLE ? nullptr : L.i8_xcd + XCD_TABLE_TICKS;
+    }
     if (mode == MODE_SAMPLE) {
         // Cosine batches whose filter pass takes the resident-query form sample in it too, when every row stream gets at
         // least four units of sample tiles (the bench: 763 sample tiles = 382 units over 32 streams per query tile; a

@@ -27,12 +27,16 @@ __global__ __launch_bounds__(R_THREADS, 1) void scan_tiles_i8d_kernel(ScanArgs a
     const uint32_t bid = blockIdx.x;
     const uint32_t xcd = bid & 7u, slot = bid >> 3;       // workgroup b runs on XCD b % 8
     const uint32_t qt = slot % n_qt, st = slot / n_qt;    // the query tile it holds, its row stream on this XCD
-    if (st >= (n_streams >> 3)) return;
+    const uint32_t streams_x = n_streams >> 3;
+    if (st >= streams_x) return;
     const uint32_t stream = st * 8u + xcd;
-    if (stream >= n_units) return;
+    // this XCD's range of units (xcd_deal.h); whatever the table holds, no unit lies past the launch's last
+    const uint32_t off_lo = a.xcd_off[xcd], off_hi = a.xcd_off[xcd + 1u] < n_units ? a.xcd_off[xcd + 1u] : n_units;
+    if (xcd_deal_unit(off_lo, off_hi, streams_x, st, 0u) >= n_units) return;
+    if (a.xcd_ticks && threadIdx.x == 0) a.xcd_ticks[(stream * n_qt + qt) * XCD_TICKS_PER_WG] = static_cast<uint32_t>(wall_clock64()) | 1u; // (0 = not written)
 
 #ifdef YAMS_ACCEL_MEASURE
-    const uint64_t t_begin = wall_clock64();
+    const uint64_t t_begin = wall_clock64(), c_begin = clock64();
 #endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -47,7 +51,7 @@ __global__ __launch_bounds__(R_THREADS, 1) void scan_tiles_i8d_kernel(ScanArgs a
     const uint32_t piece_row_stride = static_cast<uint32_t>(nslab) * 1024u; // bytes between the pieces of consecutive 16-row blocks
 
     struct Geo { uint64_t row0; const unsigned char* base; };
-    auto unit_of = [&](uint32_t k) __attribute__((always_inline)) -> uint32_t { return stream + (k >> 1) * n_streams; };
+    auto unit_of = [&](uint32_t k) __attribute__((always_inline)) -> uint32_t { return xcd_deal_unit(off_lo, off_hi, streams_x, st, k >> 1); }; // (0xffffffff past the stream's end)
     auto locate = [&](uint32_t k, Geo& g) __attribute__((always_inline)) {
         const uint32_t un_ = unit_of(k);
         const uint32_t sel = un_ < n_units ? 2u * un_ + (k & 1u) : 0xffffffffu;
@@ -313,13 +317,18 @@ __global__ __launch_bounds__(R_THREADS, 1) void scan_tiles_i8d_kernel(ScanArgs a
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]), "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fa[1][2]),
                  "+v"(fa[1][3]), "+v"(fa[2][0]), "+v"(fa[2][1]), "+v"(fa[2][2]), "+v"(fa[2][3]) :: "memory");
     zs_flush();
-    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) a.log_cnt[log_region] = log_pos < a.log_cap ? log_pos : a.log_cap;
+    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) {
+        a.log_cnt[log_region] = log_pos < a.log_cap ? log_pos : a.log_cap;
+        // when this wave ended: the next batch's deal of units to the XCDs learns from it (prep_i8_kernel)
+        if (a.xcd_ticks) a.xcd_ticks[(stream * n_qt + qt) * XCD_TICKS_PER_WG + 1u + static_cast<uint32_t>(wid)] = static_cast<uint32_t>(wall_clock64()) | 1u;
+    }
 #ifdef YAMS_ACCEL_MEASURE
     if (lane == 0 && n_qt <= 8) {
         uint32_t* const dbg = a.i8_sync + (static_cast<uint64_t>(n_streams) * 4u + static_cast<uint64_t>(stream) * 8u + static_cast<uint32_t>(wid)) * 32u;
         dbg[8 + qt] = static_cast<uint32_t>(t_begin);
         dbg[16 + qt] = static_cast<uint32_t>(wall_clock64());
         dbg[24 + qt] = units_read;
+        dbg[qt] = static_cast<uint32_t>((clock64() - c_begin) * 100ull / (wall_clock64() - t_begin + 1)); // MHz: the shader clock the wave ran at
     }
 #endif
 }

@@ -1,6 +1,7 @@
 // scan_launch.h — host-visible launch descriptors for scan_kernels.hip.
 #pragma once
 #include "common.h"
+#include "xcd_deal.h"
 
 namespace yams_accel {
 
@@ -17,6 +18,7 @@ struct ScanLaunch {
     uint64_t* log_key = nullptr; uint32_t* log_q = nullptr; uint32_t* log_cnt = nullptr; uint32_t log_cap = 0;
     uint32_t* q_over = nullptr;
     uint32_t* i8_sync = nullptr;         // resident-query form of the int8 filter: pacing counters (i8_sync_words())
+    uint32_t* i8_xcd = nullptr;          // ... and the deal of its units to the XCDs (xcd_deal.h: weights, off[], end ticks; i8_xcd_deal_plan())
     // int8 tier under L2 (launch_i8_l2_*): thresholds meta {s_b, -nmin_b}, row / query biases
     bool i8_l2 = false;
     const float* i8_l2_meta = nullptr;
@@ -100,10 +102,18 @@ inline uint32_t bf16_slab_k(int passes, uint32_t dim) { return (passes == 1 && (
 hipError_t launch_scan_bf16(hipStream_t st, const ScanLaunch& L, int metric, int mode, int passes, int version);
 // The INT8 tier (cosine, dim % 64 == 0, int8 shadow present): sample (mode 0) or filter (mode 1) pass.
 hipError_t launch_scan_i8(hipStream_t st, const ScanLaunch& L, int mode, int version);
+// The deal of the resident-query sweep's units to the XCDs (xcd_deal.h).  One workgroup of prep_i8_kernel turns the end ticks
+// the previous filter launch of this context left in `table` into the running weights and writes off[] for this batch's
+// two launches; mode: feedback (the product's), equal weights (a context's first batch on a plan, or after the plan
+// changed: the table's contents are not read), forced (measurement build: the tests and A/B runs).
+// (enum XCD_DEAL_* and struct XcdDealPrep: xcd_deal.h)
+// the plan of this launch's deal (false: the launch does not take the resident-query form, there is no deal); table_words:
+// the size of `table`
+bool i8_xcd_deal_plan(const ScanLaunch& L, XcdDealPrep* p, uint64_t* table_words);
 // Quantises the prepared (unit) queries of a batch: k-slab-major int8 plane + {t_q, c_q, f_q} per query.
 hipError_t launch_prep_i8(hipStream_t st, const float* qprep, uint32_t nq, uint32_t q_pad, uint32_t dim,
                           int8_t* q_i8, float* q_meta, bool raw_queries = false, uint32_t* zero_words = nullptr,
-                          uint64_t n_zero_words = 0, bool rotated = false);
+                          uint64_t n_zero_words = 0, bool rotated = false, const XcdDealPrep* deal = nullptr);
 // L2 on the int8 tier.  Per batch and shard: (1) norm statistics of the shard — per 64-row block the smallest row norm,
 // shard-wide the norm range, the largest in-block spread in units of the block scale, and the rows whose squared
 // norm lies outside norm_in_range() (counted and listed: unconditional candidates); stats = 8 words, zeroed first.
