@@ -1013,6 +1013,101 @@ YAMS_ACCEL_API yams_status_t yams_quality_persistence_h0_host(
     yams_persistence_h0_t* out, double* out_distances, double* out_merge_weights, float* out_stage_ms);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Topology input features: chunk aggregation, variance weights, the composed feature vector   */
+/* ------------------------------------------------------------------------------------------ */
+/* Every stage of the topology rebuild starts from the n x dim matrix of per-document feature vectors that
+ * TopologyInputExtractor::extract (src/topology/topology_input_extractor.cpp:517-745) composes on one host core.  These entries
+ * are its array arithmetic; the shell that keeps the record admissions, the sample cap, the selection of the kept dimensions
+ * (the host's own std::partial_sort), the conditions of :353-354 and :169-171, and probes which variance form the host's
+ * build has, is include/yams_accel/topology_features.hpp.  The contract, restated:
+ *   aggregate (:397-430)  per (document, dimension) ONE fp32 chain in one lane over the document's record list IN THE ORDER
+ *             GIVEN: the first record is ASSIGNED (:411: its bits are kept, a lone -0.0f stays -0.0f, a NaN keeps its payload;
+ *             the centroid entry starts from 0.0f + and would return +0.0f), every later record is added (:419), and for
+ *             count > 1 the sum is divided by float(count), the IEEE divide (:424-428).  count == 0: a row of zeros, count 0.
+ *             The short-circuit on a DOCUMENT-level record (:398-402), the skip of empty records (:407) and of records whose
+ *             size differs from the first contributing one (:415) are the shell's: the list holds the contributing records.
+ *   variance (:123-152)  per dimension: mean = the fp64 chain mean += double(e) over the sample rows in sample order, then
+ *             /= double(m); then d = double(e) - mean, var += d * d in the same order, then /= double(m).  d carries up to 53
+ *             bits, so d * d is NOT exact and the bits of `var += d * d` depend on whether the host's compiler contracted it
+ *             into an fma: YAMS_RESIDUAL_SEPARATE = a rounded multiply, then a rounded add; YAMS_RESIDUAL_FUSED = one fma.
+ *             The shell probes which one the host's build is.  A CHAIN IS NEVER SPLIT: the parallelism is across dimensions
+ *             only (one lane per dimension), so the call is a LATENCY CHAIN of 2 * m dependent fp64 steps, whatever dim is.
+ *             The selection of the top targetDim variances (:156-163) stays on the host: the order of equal variances at the
+ *             cut is std::partial_sort's.
+ *   compose (:344-388)  per row, in the reference's order:
+ *             matryoshka view (:172-186), when `weights` is given: kept = the indices with weights[i] > 0.0f, ascending (a
+ *             NaN weight is not kept; the count need not equal any target); coarse[j] = dense[kept[j]] * weights[kept[j]], an
+ *             fp32 multiply; then the normalisation.  Without `weights` the normalisation applies to dense itself.
+ *             normalisation (:98-110): sumSq = one fp64 chain of double(x) * double(x) in element order (exact products:
+ *             form-free); sumSq <= 0.0 leaves the vector as it is (a NaN sumSq does not take that branch); otherwise
+ *             norm = float(sqrt(sumSq)) and every element is x / norm in fp32.  A norm that rounds to 0.0f or to inf is
+ *             served as IEEE gives it (inf or NaN elements; zeros).
+ *             sketch (:192-203): count[sig[i] % sketch_dim] per bucket, taken as float(count) — the reference's `+= 1.0F`
+ *             chain while sig_len < 2^24; the limit is YAMS_FEATURES_MAX_SIG_LEN — then normalised the same way.  (The
+ *             counts are integers summing to sig_len, so every partial sum of their squares is an integer <= 2^32: the chain
+ *             is exact in any order.)
+ *             concatenation (:362-387): entityOn = entity && K && entity_on[i]; minhashOn = sig && sig_len && sketch_on[i] &&
+ *             sketch_dim > 0.  Both off: the row is the dense part alone, with NO multiply.  Otherwise aE = entityOn ?
+ *             alpha_e : 0.0f, aM likewise, aD = std::max(0.0f, (1.0f - aE) - aM) in fp32 = (0.0f < t) ? t : 0.0f (a NaN gives
+ *             0.0f), and the row is dense * aD, then entity * aE if on, then sketch * aM if on.  f32 denormals are kept.
+ * Results equal the CPU loop bit for bit in the form asked for (a NaN is the reference's NaN where no arithmetic touches it,
+ * some NaN otherwise).  Every input value is served as IEEE gives it (NaN, inf, +-0.0).
+ * Lists are CSR: offsets [lists + 1] uint64 starting at 0 and never decreasing, entries uint32.
+ * Limits: dim, K, sketch_dim <= YAMS_FEATURES_MAX_DIM, sig_len <= YAMS_FEATURES_MAX_SIG_LEN, n (n_records, n_docs) < 2^31,
+ * entries < 2^32: beyond, YAMS_ERR_UNSUPPORTED.  dim == 0, a null array that is needed, offsets that do not start at 0 or
+ * decrease, an index out of range, an unknown form, out_stride smaller than the longest possible row, an output overlapping an
+ * input: YAMS_ERR_INVALID_ARG, found before anything is written.  Every call synchronises the context's stream before
+ * returning.  The _host twins take host arrays throughout. */
+#define YAMS_FEATURES_MAX_DIM 4096u
+#define YAMS_FEATURES_MAX_SIG_LEN 65536u
+/* aggregateEmbedding of every document at once.
+ *   rows         [n_records][dim] fp32: the chunk embeddings (any values)
+ *   doc_offsets  [n_docs + 1] uint64       records  uint32 row indices < n_records, per document in the order of the sums
+ *   out          [n_docs][dim] fp32        out_counts  [n_docs] uint32: the contributing records
+ * n_docs == 0: YAMS_OK, nothing written.  One chain per (document, dimension), one lane each. */
+YAMS_ACCEL_API yams_status_t yams_features_aggregate_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n_records, uint32_t dim, const uint64_t* doc_offsets, const uint32_t* records,
+    uint64_t n_docs, float* out, uint32_t* out_counts);
+YAMS_ACCEL_API yams_status_t yams_features_aggregate_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n_records, uint32_t dim, const uint64_t* doc_offsets, const uint32_t* records,
+    uint64_t n_docs, float* out, uint32_t* out_counts);
+/* The two passes of computeVarianceWeights.
+ *   rows              [n][dim] fp32
+ *   select, n_select  nullable: m = n_select sample rows (indices < n) in the order of the sums, repeats allowed; NULL = the
+ *                     rows 0 .. n-1 (m = n, n_select ignored)
+ *   form              YAMS_RESIDUAL_SEPARATE or YAMS_RESIDUAL_FUSED
+ *   out_mean, out_var [dim] fp64 each
+ * m == 0: YAMS_OK, nothing written (the reference returns before it divides, :134-136).  The _host twin sends only the sample
+ * rows. */
+YAMS_ACCEL_API yams_status_t yams_features_variance_device(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select, uint32_t form,
+    double* out_mean, double* out_var);
+YAMS_ACCEL_API yams_status_t yams_features_variance_host(
+    yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select, uint32_t form,
+    double* out_mean, double* out_var);
+/* composeFeatureVector of every row at once.
+ *   dense       [n][dim] fp32: the dense view
+ *   weights     [dim] fp32, HOST memory in both twins, nullable: the matryoshka weights of the shell's host-side selection;
+ *               NULL = matryoshka off
+ *   entity      [n][K] fp32, nullable: entity signatures, already normalised by the host, taken as given
+ *   entity_on   [n] uint8: the per-row switch of the entity part (needed when entity && K)
+ *   sig         [n][sig_len] uint32, nullable: MinHash signatures
+ *   sketch_on   [n] uint8: the per-row switch of the sketch part (needed when sig && sig_len && sketch_dim)
+ *   out         [n][out_stride] fp32; out_dims [n] uint32: the row's length; everything behind it in the row is zero-filled.
+ *               The longest possible row is kept (or dim) + (entity && K ? K : 0) + (sig && sig_len && sketch_dim ?
+ *               sketch_dim : 0).
+ * n == 0: YAMS_OK, nothing written.  Each row's sumSq is one chain in one lane; the scale-and-store pass is parallel across
+ * elements. */
+YAMS_ACCEL_API yams_status_t yams_features_compose_device(
+    yams_accel_ctx* ctx, const float* dense, uint64_t n, uint32_t dim, const float* weights, const float* entity, uint32_t k,
+    const uint8_t* entity_on, const uint32_t* sig, uint32_t sig_len, const uint8_t* sketch_on, uint32_t sketch_dim, float alpha_e,
+    float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims);
+YAMS_ACCEL_API yams_status_t yams_features_compose_host(
+    yams_accel_ctx* ctx, const float* dense, uint64_t n, uint32_t dim, const float* weights, const float* entity, uint32_t k,
+    const uint8_t* entity_on, const uint32_t* sig, uint32_t sig_len, const uint8_t* sketch_on, uint32_t sketch_dim, float alpha_e,
+    float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims);
+
+/* ------------------------------------------------------------------------------------------ */
 /* The semantic-neighbour graph: exact top-K self-join of the document-level embeddings         */
 /* ------------------------------------------------------------------------------------------ */
 /* EmbeddingService::updateSemanticNeighborGraphUnlocked (src/daemon/components/EmbeddingService.cpp) scores, for every
@@ -1636,6 +1731,27 @@ typedef struct yams_topology_quality_v1 {
                                     uint32_t form, yams_persistence_h0_t* out, double** out_distances, double** out_merge_weights);
     void (*free_persistence_h0)(void* self, double* distances, double* merge_weights);
 } yams_topology_quality_v1;
+
+/* The topology build's input features (yams_features_aggregate_host / _variance_host / _compose_host) for a host that holds the
+ * embeddings in its own memory.  A separate interface, version 1, served by yams_plugin_get_interface and NOT listed in the
+ * manifest, for the reason given at vector_doc_scan_v1.  Host memory in, host memory out: every output is the caller's array.
+ * Statuses and limits of the flat entries. */
+#define YAMS_IFACE_TOPOLOGY_FEATURES_V1 "topology_features_v1"
+#define YAMS_IFACE_TOPOLOGY_FEATURES_V1_VERSION 1u
+typedef struct yams_topology_features_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_TOPOLOGY_FEATURES_V1_VERSION */
+    void* self;
+    /* out: the caller's [n_docs][dim]; out_counts: [n_docs] */
+    yams_status_t (*aggregate)(void* self, const float* rows, uint64_t n_records, uint32_t dim, const uint64_t* doc_offsets,
+                               const uint32_t* records, uint64_t n_docs, float* out, uint32_t* out_counts);
+    /* out_mean / out_var: the caller's [dim] */
+    yams_status_t (*variance)(void* self, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select,
+                              uint32_t form, double* out_mean, double* out_var);
+    /* out: the caller's [n][out_stride]; out_dims: [n] */
+    yams_status_t (*compose)(void* self, const float* dense, uint64_t n, uint32_t dim, const float* weights, const float* entity,
+                             uint32_t k, const uint8_t* entity_on, const uint32_t* sig, uint32_t sig_len, const uint8_t* sketch_on,
+                             uint32_t sketch_dim, float alpha_e, float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims);
+} yams_topology_features_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

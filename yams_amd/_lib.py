@@ -300,6 +300,22 @@ class TopologyQualityV1(C.Structure):  # topology_quality_v1 (served by get_inte
     ]
 
 
+FEATURES_MAX_DIM, FEATURES_MAX_SIG_LEN = 4096, 65536           # YAMS_FEATURES_MAX_*
+_FEATURES_AGGREGATE = [vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp]
+_FEATURES_VARIANCE = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_uint32, vp, vp]
+_FEATURES_COMPOSE = [vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_float, C.c_float, vp,
+                     C.c_uint32, vp]
+
+
+class TopologyFeaturesV1(C.Structure):  # topology_features_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("aggregate", C.CFUNCTYPE(C.c_int, vp, *_FEATURES_AGGREGATE)),
+        ("variance", C.CFUNCTYPE(C.c_int, vp, *_FEATURES_VARIANCE)),
+        ("compose", C.CFUNCTYPE(C.c_int, vp, *_FEATURES_COMPOSE)),
+    ]
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -374,6 +390,8 @@ EXPORTS = [
     "yams_route_index_create_device", "yams_route_index_create_host", "yams_route_index_destroy", "yams_route_index_info",
     "yams_route_dense_device", "yams_route_dense_host",
     "yams_quality_persistence_h0_device", "yams_quality_persistence_h0_host",
+    "yams_features_aggregate_device", "yams_features_aggregate_host", "yams_features_variance_device", "yams_features_variance_host",
+    "yams_features_compose_device", "yams_features_compose_host",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -484,6 +502,12 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
         fn.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(RouteDiag)]
     for fn in (L.yams_quality_persistence_h0_device, L.yams_quality_persistence_h0_host):
         fn.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.POINTER(PersistenceH0), vp, vp, vp]
+    for fn in (L.yams_features_aggregate_device, L.yams_features_aggregate_host):
+        fn.argtypes = [vp, *_FEATURES_AGGREGATE]
+    for fn in (L.yams_features_variance_device, L.yams_features_variance_host):
+        fn.argtypes = [vp, *_FEATURES_VARIANCE]
+    for fn in (L.yams_features_compose_device, L.yams_features_compose_host):
+        fn.argtypes = [vp, *_FEATURES_COMPOSE]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

@@ -829,6 +829,74 @@ class Accel:
             out["weights"] = w
         return out
 
+    # ---- topology input features (yams_features_*) -----------------------------------------------------------------------------
+    def features_aggregate(self, rows: np.ndarray, doc_offsets, records, host_entry: bool = False, misalign: int = 0):
+        """aggregateEmbedding of every document (yams_features_aggregate_device / _host): rows [n_records][dim] float32, CSR
+        record lists in the order of the sums.  Returns (out [n_docs][dim] float32, counts [n_docs] uint32)."""
+        x = np.ascontiguousarray(rows, np.float32)
+        n, dim = x.shape
+        off = np.ascontiguousarray(doc_offsets, np.uint64)
+        rec = np.ascontiguousarray(records, np.uint32)
+        d = len(off) - 1
+        out, cnt = self._artifact_call(
+            self.L.yams_features_aggregate_device, self.L.yams_features_aggregate_host, host_entry,
+            [x if x.size else None, off, rec if rec.size else None], [(np.float32, d * dim), (np.uint32, d)],
+            lambda i, o: (i[0], n, dim, i[1], i[2], d, o[0], o[1]), misalign)
+        return out.reshape(d, dim), cnt
+
+    def features_variance(self, rows: np.ndarray, select=None, form: int = _lib.RESIDUAL_SEPARATE, host_entry: bool = False,
+                          misalign: int = 0):
+        """The two passes of computeVarianceWeights over rows[select] in order (all rows without select):
+        yams_features_variance_device / _host.  Returns (mean [dim], var [dim]) float64, or (None, None) when m == 0 (nothing
+        is written then: the guard words are checked)."""
+        x = np.ascontiguousarray(rows, np.float32)
+        n, dim = x.shape
+        sel = None if select is None else np.ascontiguousarray(select, np.uint32)
+        m = n if sel is None else len(sel)
+        if sel is not None and sel.size == 0:
+            sel = np.zeros(1, np.uint32)
+        if m == 0:      # written nowhere: every byte of the outputs must still be the guard
+            guard = self._GUARD
+            mean, var = self._artifact_call(
+                self.L.yams_features_variance_device, self.L.yams_features_variance_host, host_entry,
+                [x if x.size else None, sel], [(np.uint8, dim * 8), (np.uint8, dim * 8)],
+                lambda i, o: (i[0], n, dim, i[1], m, form, o[0], o[1]), misalign)
+            assert (mean == guard).all() and (var == guard).all(), "m == 0 wrote to an output"
+            return None, None
+        mean, var = self._artifact_call(
+            self.L.yams_features_variance_device, self.L.yams_features_variance_host, host_entry,
+            [x if x.size else None, sel], [(np.float64, dim), (np.float64, dim)],
+            lambda i, o: (i[0], n, dim, i[1], m, form, o[0], o[1]), misalign)
+        return mean, var
+
+    def features_compose(self, dense: np.ndarray, weights=None, entity=None, entity_on=None, sig=None, sketch_on=None,
+                         sketch_dim: int = 0, alpha_e: float = 0.0, alpha_m: float = 0.0, out_stride=None, host_entry: bool = False,
+                         misalign: int = 0):
+        """composeFeatureVector of every row (yams_features_compose_device / _host).  weights [dim] float32 or None (host
+        memory in both twins); entity [n][K] float32 or None; sig [n][sig_len] uint32 or None.  Returns (out [n][out_stride]
+        float32, dims [n] uint32); out_stride defaults to the longest possible row."""
+        x = np.ascontiguousarray(dense, np.float32)
+        n, dim = x.shape
+        w = None if weights is None else np.ascontiguousarray(weights, np.float32)
+        ent = None if entity is None else np.ascontiguousarray(entity, np.float32)
+        eon = None if entity_on is None else np.ascontiguousarray(entity_on, np.uint8)
+        sg = None if sig is None else np.ascontiguousarray(sig, np.uint32)
+        son = None if sketch_on is None else np.ascontiguousarray(sketch_on, np.uint8)
+        k = 0 if ent is None else ent.shape[1]
+        sig_len = 0 if sg is None else sg.shape[1]
+        if out_stride is None:
+            kc = dim if w is None else int((w > 0).sum())
+            out_stride = kc + (k if ent is not None else 0) + (sketch_dim if sg is not None and sig_len and sketch_dim else 0)
+
+        def some(a):      # an array without elements still has to be an address
+            return None if a is None else (a if a.size else np.zeros(4, a.dtype))
+        out, dims = self._artifact_call(
+            self.L.yams_features_compose_device, self.L.yams_features_compose_host, host_entry,
+            [x if x.size else None, some(ent), some(eon), some(sg), some(son)], [(np.float32, n * out_stride), (np.uint32, n)],
+            lambda i, o: (i[0], n, dim, None if w is None else w.ctypes.data, i[1], k, i[2], i[3], sig_len, i[4], sketch_dim, alpha_e,
+                          alpha_m, o[0], out_stride, o[1]), misalign)
+        return out.reshape(n, out_stride), dims
+
     # ---- cluster routing (yams_route_index_* / yams_route_dense_*) ----------------------------------------------------------
     def route_index(self, vectors: np.ndarray, cluster_offsets, has_centroid, position, host_entry: bool = False,
                     misalign: int = 0) -> "RouteIndex":

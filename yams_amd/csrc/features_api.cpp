@@ -1,0 +1,325 @@
+// features_api.cpp — yams_features_aggregate / _variance / _compose (_device and _host): the array arithmetic of
+// TopologyInputExtractor::extract (aggregateEmbedding, computeVarianceWeights' two passes, composeFeatureVector) behind the C
+// ABI.  Every entry: the limits (no device needed) -> argument checks -> the list totals read back -> ONE read-back of the check
+// flags -> the work.  Nothing is written to an output before every refusal is known.
+#include <cstring>
+#include <vector>
+
+#include "accel_ctx.h"
+#include "features_launch.h"
+
+using namespace yams_accel;
+
+namespace yams_accel {
+// artifact_kernels.hip: flags |= 1 for offsets that do not start at 0, decrease or pass `total`; |= 2 for an index >= limit
+hipError_t launch_artifact_check(hipStream_t st, const uint64_t* off, uint64_t lists, uint64_t total, const uint32_t* idx, uint32_t limit,
+                                 uint32_t* flags);
+}
+
+namespace {
+
+static_assert(YAMS_FEATURES_MAX_DIM == kFeatMaxDim && YAMS_FEATURES_MAX_SIG_LEN == kFeatMaxSigLen, "the header's limits are the launchers'");
+constexpr uint64_t kMaxRows = 1ull << 31;
+constexpr uint64_t kMaxEntries = 1ull << 32;
+
+bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    if (!a || !b || !a_bytes || !b_bytes) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+// The list checks on the device: offsets from 0, never decreasing, ending at `total`; entries < limit.  Synchronises.
+yams_status_t check_lists(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t lists, uint64_t total, const uint32_t* d_idx, uint32_t limit,
+                          const char* what) {
+    hipStream_t st = ctx->stream;
+    uint32_t* d_flags; uint32_t* h_flags;
+    YA_TRY(ws_get(ctx, "feat_flags", 16, (void**)&d_flags));
+    YA_TRY(pinned_get(ctx, 64, (void**)&h_flags));
+    YA_HIP(ctx, hipMemsetAsync(d_flags, 0, 16, st));
+    YA_HIP(ctx, launch_artifact_check(st, d_off, d_off ? lists : 0, total, d_idx, limit, d_flags));
+    YA_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, 4, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    if (*h_flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": the offsets do not start at 0 or decrease");
+    if (*h_flags & 2u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": an index is out of range");
+    return YAMS_OK;
+}
+
+// ---- aggregate: what needs no device ---------------------------------------------------------------------------------------
+yams_status_t check_aggregate(yams_accel_ctx* ctx, uint64_t n_records, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs,
+                              const float* out, const uint32_t* out_counts) {
+    if (n_records >= kMaxRows || n_docs >= kMaxRows) return fail(ctx, YAMS_ERR_UNSUPPORTED, "n_records and n_docs must be < 2^31");
+    if (dim > YAMS_FEATURES_MAX_DIM) return fail(ctx, YAMS_ERR_UNSUPPORTED, "dim exceeds YAMS_FEATURES_MAX_DIM");
+    if (dim == 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "dim == 0");
+    if (n_docs && (!doc_offsets || !out || !out_counts)) return fail(ctx, YAMS_ERR_INVALID_ARG, "null doc_offsets or output");
+    return YAMS_OK;
+}
+// once the lists' total is known
+yams_status_t check_aggregate_total(yams_accel_ctx* ctx, const float* rows, uint64_t n_records, uint32_t dim, const uint32_t* records,
+                                    uint64_t total, uint64_t n_docs, const float* out, const uint32_t* out_counts) {
+    if (total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
+    if (total && (!records || !rows)) return fail(ctx, YAMS_ERR_INVALID_ARG, "null rows or records");
+    const size_t rb = static_cast<size_t>(n_records) * dim * 4;
+    if (overlaps(out, static_cast<size_t>(n_docs) * dim * 4, rows, rb) || overlaps(out_counts, static_cast<size_t>(n_docs) * 4, rows, rb))
+        return fail(ctx, YAMS_ERR_INVALID_ARG, "an output overlaps rows");
+    return YAMS_OK;
+}
+
+// ---- variance ----------------------------------------------------------------------------------------------------------------
+yams_status_t check_variance(yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, uint64_t m, uint32_t form,
+                             const double* out_mean, const double* out_var) {
+    if (n >= kMaxRows) return fail(ctx, YAMS_ERR_UNSUPPORTED, "n must be < 2^31");
+    if (m >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "select must hold fewer than 2^32 entries");
+    if (dim > YAMS_FEATURES_MAX_DIM) return fail(ctx, YAMS_ERR_UNSUPPORTED, "dim exceeds YAMS_FEATURES_MAX_DIM");
+    if (dim == 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "dim == 0");
+    if (form != YAMS_RESIDUAL_SEPARATE && form != YAMS_RESIDUAL_FUSED) return fail(ctx, YAMS_ERR_INVALID_ARG, "unknown form");
+    if (m == 0) return YAMS_OK;
+    if (!rows || !out_mean || !out_var) return fail(ctx, YAMS_ERR_INVALID_ARG, "null rows or output");
+    const size_t rb = static_cast<size_t>(n) * dim * 4, ob = static_cast<size_t>(dim) * 8;
+    if (overlaps(out_mean, ob, rows, rb) || overlaps(out_var, ob, rows, rb) || overlaps(out_mean, ob, out_var, ob))
+        return fail(ctx, YAMS_ERR_INVALID_ARG, "an output overlaps rows or the other output");
+    return YAMS_OK;
+}
+
+// ---- compose -----------------------------------------------------------------------------------------------------------------
+struct ComposeShape { std::vector<uint32_t> kept; std::vector<float> kept_w; uint32_t kc; bool entity, sketch; uint32_t longest; };
+
+yams_status_t check_compose(yams_accel_ctx* ctx, const float* dense, uint64_t n, uint32_t dim, const float* weights, const float* entity,
+                            uint32_t k, const uint8_t* entity_on, const uint32_t* sig, uint32_t sig_len, const uint8_t* sketch_on,
+                            uint32_t sketch_dim, const float* out, uint32_t out_stride, const uint32_t* out_dims, ComposeShape* sh) {
+    if (n >= kMaxRows) return fail(ctx, YAMS_ERR_UNSUPPORTED, "n must be < 2^31");
+    if (dim > YAMS_FEATURES_MAX_DIM || k > YAMS_FEATURES_MAX_DIM || sketch_dim > YAMS_FEATURES_MAX_DIM)
+        return fail(ctx, YAMS_ERR_UNSUPPORTED, "dim, K or sketch_dim exceeds YAMS_FEATURES_MAX_DIM");
+    if (sig_len > YAMS_FEATURES_MAX_SIG_LEN) return fail(ctx, YAMS_ERR_UNSUPPORTED, "sig_len exceeds YAMS_FEATURES_MAX_SIG_LEN");
+    if (dim == 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "dim == 0");
+    sh->entity = entity && k;
+    sh->sketch = sig && sig_len && sketch_dim;
+    sh->kept.clear();
+    sh->kept_w.clear();
+    if (weights)      // :175-179 — the indices of the weights > 0.0F, ascending (a NaN is not kept)
+        for (uint32_t i = 0; i < dim; ++i)
+            if (weights[i] > 0.0f) { sh->kept.push_back(i); sh->kept_w.push_back(weights[i]); }
+    sh->kc = weights ? static_cast<uint32_t>(sh->kept.size()) : dim;
+    sh->longest = sh->kc + (sh->entity ? k : 0u) + (sh->sketch ? sketch_dim : 0u);
+    if (n == 0) return YAMS_OK;
+    if (!dense || !out_dims || (out_stride && !out)) return fail(ctx, YAMS_ERR_INVALID_ARG, "null dense or output");
+    if ((sh->entity && !entity_on) || (sh->sketch && !sketch_on)) return fail(ctx, YAMS_ERR_INVALID_ARG, "a part needs its per-row switch");
+    if (out_stride < sh->longest) return fail(ctx, YAMS_ERR_INVALID_ARG, "out_stride is smaller than the longest possible row");
+    const size_t ob = static_cast<size_t>(n) * out_stride * 4, db = static_cast<size_t>(n) * 4;
+    const struct { const void* p; size_t bytes; } in[] = {{dense, static_cast<size_t>(n) * dim * 4},
+                                                          {sh->entity ? entity : nullptr, static_cast<size_t>(n) * k * 4},
+                                                          {sh->entity ? entity_on : nullptr, static_cast<size_t>(n)},
+                                                          {sh->sketch ? sig : nullptr, static_cast<size_t>(n) * sig_len * 4},
+                                                          {sh->sketch ? sketch_on : nullptr, static_cast<size_t>(n)}};
+    for (const auto& a : in)
+        if (overlaps(out, ob, a.p, a.bytes) || overlaps(out_dims, db, a.p, a.bytes)) return fail(ctx, YAMS_ERR_INVALID_ARG, "an output overlaps an input");
+    if (overlaps(out, ob, out_dims, db)) return fail(ctx, YAMS_ERR_INVALID_ARG, "out overlaps out_dims");
+    return YAMS_OK;
+}
+
+} // namespace
+
+// ---- aggregate ---------------------------------------------------------------------------------------------------------------
+extern "C" yams_status_t yams_features_aggregate_device(yams_accel_ctx* ctx, const float* rows, uint64_t n_records, uint32_t dim,
+                                                        const uint64_t* doc_offsets, const uint32_t* records, uint64_t n_docs, float* out,
+                                                        uint32_t* out_counts) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    YA_TRY(check_aggregate(ctx, n_records, dim, doc_offsets, n_docs, out, out_counts));
+    if (n_docs == 0) return YAMS_OK;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    uint64_t* h_total;
+    YA_TRY(pinned_get(ctx, 64, (void**)&h_total));
+    YA_HIP(ctx, hipMemcpyAsync(h_total, doc_offsets + n_docs, 8, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    const uint64_t total = *h_total;
+    YA_TRY(check_aggregate_total(ctx, rows, n_records, dim, records, total, n_docs, out, out_counts));
+    YA_TRY(check_lists(ctx, doc_offsets, n_docs, total, records, static_cast<uint32_t>(n_records), "records"));
+    {
+        TimedRegion tr(ctx, "features_aggregate");
+        YA_HIP(ctx, launch_features_aggregate(st, rows, dim, doc_offsets, records, static_cast<uint32_t>(n_docs), out, out_counts));
+        tr.end();
+    }
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    return YAMS_OK;
+}
+
+extern "C" yams_status_t yams_features_aggregate_host(yams_accel_ctx* ctx, const float* rows, uint64_t n_records, uint32_t dim,
+                                                      const uint64_t* doc_offsets, const uint32_t* records, uint64_t n_docs, float* out,
+                                                      uint32_t* out_counts) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    YA_TRY(check_aggregate(ctx, n_records, dim, doc_offsets, n_docs, out, out_counts));
+    if (n_docs == 0) return YAMS_OK;
+    // judged here, before an upload is sized by them
+    if (doc_offsets[0] != 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "records: the offsets do not start at 0 or decrease");
+    for (uint64_t i = 0; i < n_docs; ++i)
+        if (doc_offsets[i + 1] < doc_offsets[i]) return fail(ctx, YAMS_ERR_INVALID_ARG, "records: the offsets do not start at 0 or decrease");
+    const uint64_t total = doc_offsets[n_docs];
+    YA_TRY(check_aggregate_total(ctx, rows, n_records, dim, records, total, n_docs, out, out_counts));
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t rb = static_cast<size_t>(n_records) * dim * 4, ob = static_cast<size_t>(n_docs) * dim * 4;
+    float* d_rows; uint64_t* d_off; uint32_t* d_rec; float* d_out; uint32_t* d_cnt;
+    YA_TRY(ws_get(ctx, "feat_host_rows", rb + 16, (void**)&d_rows));
+    YA_TRY(ws_get(ctx, "feat_host_offsets", (static_cast<size_t>(n_docs) + 1) * 8, (void**)&d_off));
+    YA_TRY(ws_get(ctx, "feat_host_list", static_cast<size_t>(total ? total : 1) * 4, (void**)&d_rec));
+    YA_TRY(ws_get(ctx, "feat_host_out", ob, (void**)&d_out));
+    YA_TRY(ws_get(ctx, "feat_host_counts", static_cast<size_t>(n_docs) * 4, (void**)&d_cnt));
+    if (rb && rows) YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
+    YA_HIP(ctx, staged_h2d(d_off, doc_offsets, (static_cast<size_t>(n_docs) + 1) * 8, st));
+    if (total) YA_HIP(ctx, staged_h2d(d_rec, records, static_cast<size_t>(total) * 4, st));
+    YA_TRY(yams_features_aggregate_device(ctx, d_rows, n_records, dim, d_off, d_rec, n_docs, d_out, d_cnt));
+    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipMemcpyAsync(out_counts, d_cnt, static_cast<size_t>(n_docs) * 4, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    return YAMS_OK;
+}
+
+// ---- variance ----------------------------------------------------------------------------------------------------------------
+extern "C" yams_status_t yams_features_variance_device(yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim,
+                                                       const uint32_t* select, uint64_t n_select, uint32_t form, double* out_mean,
+                                                       double* out_var) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    const uint64_t m = select ? n_select : n;
+    YA_TRY(check_variance(ctx, rows, n, dim, m, form, out_mean, out_var));
+    if (m == 0) return YAMS_OK;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    if (select) YA_TRY(check_lists(ctx, nullptr, 0, m, select, static_cast<uint32_t>(n), "select"));
+    {
+        TimedRegion tr(ctx, "features_variance");
+        YA_HIP(ctx, launch_features_variance(st, rows, dim, select, static_cast<uint32_t>(m), form == YAMS_RESIDUAL_FUSED, out_mean, out_var));
+        tr.end();
+    }
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    return YAMS_OK;
+}
+
+extern "C" yams_status_t yams_features_variance_host(yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim,
+                                                     const uint32_t* select, uint64_t n_select, uint32_t form, double* out_mean,
+                                                     double* out_var) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    const uint64_t m = select ? n_select : n;
+    YA_TRY(check_variance(ctx, rows, n, dim, m, form, out_mean, out_var));
+    if (m == 0) return YAMS_OK;
+    for (uint64_t i = 0; select && i < m; ++i)
+        if (select[i] >= n) return fail(ctx, YAMS_ERR_INVALID_ARG, "select: an index is out of range");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    // only the sample rows travel, packed in the order of the sums
+    std::vector<float> packed;
+    const float* src = rows;
+    if (select) {
+        packed.resize(static_cast<size_t>(m) * dim);
+        for (uint64_t i = 0; i < m; ++i)
+            std::memcpy(packed.data() + static_cast<size_t>(i) * dim, rows + static_cast<size_t>(select[i]) * dim, static_cast<size_t>(dim) * 4);
+        src = packed.data();
+    }
+    const size_t rb = static_cast<size_t>(m) * dim * 4;
+    float* d_rows; double* d_out;
+    YA_TRY(ws_get(ctx, "feat_host_rows", rb + 16, (void**)&d_rows));
+    YA_TRY(ws_get(ctx, "feat_host_moments", static_cast<size_t>(dim) * 16, (void**)&d_out));
+    YA_HIP(ctx, staged_h2d(d_rows, src, rb, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));      // `packed` goes away
+    YA_TRY(yams_features_variance_device(ctx, d_rows, m, dim, nullptr, 0, form, d_out, d_out + dim));
+    YA_HIP(ctx, hipMemcpyAsync(out_mean, d_out, static_cast<size_t>(dim) * 8, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipMemcpyAsync(out_var, d_out + dim, static_cast<size_t>(dim) * 8, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    return YAMS_OK;
+}
+
+// ---- compose -----------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The work over device arrays; sh is check_compose's.  Synchronises.
+yams_status_t run_compose(yams_accel_ctx* ctx, const ComposeShape& sh, FeatComposeArgs a) {
+    hipStream_t st = ctx->stream;
+    a.kc = sh.kc;
+    a.kept = nullptr;
+    a.kept_w = nullptr;
+    if (!sh.entity) a.entity = nullptr;
+    if (!sh.sketch) a.sig = nullptr;
+    double* d_nsq = nullptr;
+    if (sh.kc) YA_TRY(ws_get(ctx, "feat_nsq", static_cast<size_t>(a.n) * 8, (void**)&d_nsq));
+    if (!sh.kept.empty()) {      // the kept columns and their weights: pinned, so that the copy may outlive this frame
+        uint32_t* d_kept; uint8_t* h_pin;
+        const size_t kb = static_cast<size_t>(sh.kc) * 4;
+        YA_TRY(ws_get(ctx, "feat_kept", kb * 2, (void**)&d_kept));
+        YA_TRY(pinned_get(ctx, kb * 2, (void**)&h_pin));
+        std::memcpy(h_pin, sh.kept.data(), kb);
+        std::memcpy(h_pin + kb, sh.kept_w.data(), kb);
+        YA_HIP(ctx, hipMemcpyAsync(d_kept, h_pin, kb * 2, hipMemcpyHostToDevice, st));
+        a.kept = d_kept;
+        a.kept_w = reinterpret_cast<const float*>(d_kept + sh.kc);
+    }
+    a.nsq = d_nsq;
+    TimedRegion tr(ctx, "features_compose");
+    hipError_t e = launch_features_row_nsq(st, a.dense, a.n, a.dim, a.kept, a.kept_w, a.kc, d_nsq);
+    if (e == hipSuccess) e = launch_features_compose_store(st, a);
+    if (e == hipSuccess) e = launch_features_compose_sketch(st, a);
+    tr.end();
+    YA_HIP(ctx, e);
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    return YAMS_OK;
+}
+
+} // namespace
+
+extern "C" yams_status_t yams_features_compose_device(yams_accel_ctx* ctx, const float* dense, uint64_t n, uint32_t dim, const float* weights,
+                                                      const float* entity, uint32_t k, const uint8_t* entity_on, const uint32_t* sig,
+                                                      uint32_t sig_len, const uint8_t* sketch_on, uint32_t sketch_dim, float alpha_e,
+                                                      float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    ComposeShape sh;
+    YA_TRY(check_compose(ctx, dense, n, dim, weights, entity, k, entity_on, sig, sig_len, sketch_on, sketch_dim, out, out_stride, out_dims, &sh));
+    if (n == 0) return YAMS_OK;
+    (void)hipSetDevice(ctx->device);
+    FeatComposeArgs a{};
+    a.dense = dense; a.n = n; a.dim = dim;
+    a.entity = entity; a.k = k; a.entity_on = entity_on;
+    a.sig = sig; a.sig_len = sig_len; a.sketch_on = sketch_on; a.sketch_dim = sketch_dim;
+    a.alpha_e = alpha_e; a.alpha_m = alpha_m;
+    a.out = out; a.out_stride = out_stride; a.out_dims = out_dims;
+    return run_compose(ctx, sh, a);
+}
+
+extern "C" yams_status_t yams_features_compose_host(yams_accel_ctx* ctx, const float* dense, uint64_t n, uint32_t dim, const float* weights,
+                                                    const float* entity, uint32_t k, const uint8_t* entity_on, const uint32_t* sig,
+                                                    uint32_t sig_len, const uint8_t* sketch_on, uint32_t sketch_dim, float alpha_e,
+                                                    float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    ComposeShape sh;
+    YA_TRY(check_compose(ctx, dense, n, dim, weights, entity, k, entity_on, sig, sig_len, sketch_on, sketch_dim, out, out_stride, out_dims, &sh));
+    if (n == 0) return YAMS_OK;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t nn = static_cast<size_t>(n);
+    const size_t db = nn * dim * 4, eb = nn * k * 4, sb = nn * sig_len * 4, ob = nn * out_stride * 4;
+    float* d_dense; float* d_ent = nullptr; uint8_t* d_eon = nullptr; uint32_t* d_sig = nullptr; uint8_t* d_son = nullptr; float* d_out; uint32_t* d_dims;
+    YA_TRY(ws_get(ctx, "feat_host_rows", db + 16, (void**)&d_dense));
+    YA_TRY(ws_get(ctx, "feat_host_out", ob + 16, (void**)&d_out));
+    YA_TRY(ws_get(ctx, "feat_host_counts", nn * 4, (void**)&d_dims));
+    YA_HIP(ctx, staged_h2d(d_dense, dense, db, st));
+    if (sh.entity) {
+        YA_TRY(ws_get(ctx, "feat_host_entity", eb, (void**)&d_ent));
+        YA_TRY(ws_get(ctx, "feat_host_entity_on", nn, (void**)&d_eon));
+        YA_HIP(ctx, staged_h2d(d_ent, entity, eb, st));
+        YA_HIP(ctx, staged_h2d(d_eon, entity_on, nn, st));
+    }
+    if (sh.sketch) {
+        YA_TRY(ws_get(ctx, "feat_host_sig", sb, (void**)&d_sig));
+        YA_TRY(ws_get(ctx, "feat_host_sketch_on", nn, (void**)&d_son));
+        YA_HIP(ctx, staged_h2d(d_sig, sig, sb, st));
+        YA_HIP(ctx, staged_h2d(d_son, sketch_on, nn, st));
+    }
+    FeatComposeArgs a{};
+    a.dense = d_dense; a.n = n; a.dim = dim;
+    a.entity = d_ent; a.k = k; a.entity_on = d_eon;
+    a.sig = d_sig; a.sig_len = sig_len; a.sketch_on = d_son; a.sketch_dim = sketch_dim;
+    a.alpha_e = alpha_e; a.alpha_m = alpha_m;
+    a.out = d_out; a.out_stride = out_stride; a.out_dims = d_dims;
+    YA_TRY(run_compose(ctx, sh, a));
+    if (ob) YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipMemcpyAsync(out_dims, d_dims, nn * 4, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    return YAMS_OK;
+}

@@ -1,8 +1,8 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// twelve interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, topology_quality_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
+// thirteen interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
+// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, topology_quality_v1, topology_features_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
@@ -1468,6 +1468,32 @@ void tq_free_persistence_h0(void*, double* distances, double* merge_weights) { s
 yams_topology_quality_v1 g_topology_quality = {YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION, nullptr, GUARDED(tq_persistence_h0),
                                                GUARDED(tq_free_persistence_h0)};
 
+// ---- topology_features_v1: the topology build's input features over host memory (yams_features_*_host) ----------------------
+// every output is the caller's array: every check is the flat entry's
+yams_status_t tf_aggregate(void*, const float* rows, uint64_t n_records, uint32_t dim, const uint64_t* doc_offsets, const uint32_t* records,
+                           uint64_t n_docs, float* out, uint32_t* out_counts) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    return yams_features_aggregate_host(lease.v, rows, n_records, dim, doc_offsets, records, n_docs, out, out_counts);
+}
+yams_status_t tf_variance(void*, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select, uint32_t form,
+                          double* out_mean, double* out_var) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    return yams_features_variance_host(lease.v, rows, n, dim, select, n_select, form, out_mean, out_var);
+}
+yams_status_t tf_compose(void*, const float* dense, uint64_t n, uint32_t dim, const float* weights, const float* entity, uint32_t k,
+                         const uint8_t* entity_on, const uint32_t* sig, uint32_t sig_len, const uint8_t* sketch_on, uint32_t sketch_dim,
+                         float alpha_e, float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    return yams_features_compose_host(lease.v, dense, n, dim, weights, entity, k, entity_on, sig, sig_len, sketch_on, sketch_dim, alpha_e,
+                                      alpha_m, out, out_stride, out_dims);
+}
+
+yams_topology_features_v1 g_topology_features = {YAMS_IFACE_TOPOLOGY_FEATURES_V1_VERSION, nullptr, GUARDED(tf_aggregate), GUARDED(tf_variance),
+                                                 GUARDED(tf_compose)};
+
 // ---- content_checksum_v1: the compressed store's CRC-32 over host memory (yams_crc32_many_host) ------------------------------
 yams_status_t cs_crc32_many(void*, const uint8_t* const* msgs, const size_t* lens, size_t n, uint32_t* out) {
     NEED_INIT();
@@ -1751,6 +1777,7 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
         {YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1, YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1_VERSION, &g_topology_artifacts},
         {YAMS_IFACE_TOPOLOGY_ROUTE_V1, YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION, &g_topology_route},
         {YAMS_IFACE_TOPOLOGY_QUALITY_V1, YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION, &g_topology_quality},
+        {YAMS_IFACE_TOPOLOGY_FEATURES_V1, YAMS_IFACE_TOPOLOGY_FEATURES_V1_VERSION, &g_topology_features},
         {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
         {YAMS_IFACE_CONTENT_CHECKSUM_V1, YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, &g_content_checksum},
         {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};
