@@ -1108,6 +1108,71 @@ YAMS_ACCEL_API yams_status_t yams_features_compose_host(
     float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Late-interaction rerank: ColBERT MaxSim over a window of documents, and token pooling        */
+/* ------------------------------------------------------------------------------------------ */
+/* Behind every reranked search the reference scores each candidate document against the query token by token:
+ * OnnxColbertSession::Impl::computeMaxSim (plugins/onnx/onnx_colbert_session.cpp:247-259, dot at :286-293), once per document
+ * from score_documents (plugins/onnx/model_provider.cpp:1883-1888), on one host core.  The same class turns a token matrix into
+ * one embedding: maxPoolEmbeddings (:214-230) and normalizeEmbedding (:232-245).  These entries are those loops; the shell that
+ * flattens the vectors of vectors, takes dim = min of the two sides, sends ragged embedding sets back to the host and probes
+ * which form the host's build has is include/yams_accel/colbert_rerank.hpp.  The contract, restated:
+ *   maxsim   sim(q, d) = ONE fp32 chain from +0.0f over i = 0 .. dim-1 in order: YAMS_RESIDUAL_SEPARATE = sum + (a[i] * b[i]),
+ *            a rounded multiply then a rounded add; YAMS_RESIDUAL_FUSED = fmaf(a[i], b[i], sum).  Which one a host's
+ *            `sum += a[i] * b[i]` is, is a property of its build.
+ *            maxSim starts at -inf and is replaced only if sim > maxSim: a NaN sim never wins, a row of NaNs or an empty
+ *            document leaves -inf, and among equal values (zeros of both signs are equal) the first in document order stays.
+ *            score starts at +0.0f; score = score + maxSim in query-token order, ONE chain per document, never split.  An empty
+ *            query gives +0.0f.  Infinities flow as the chain carries them (+inf then -inf: NaN).  Subnormals are kept.
+ *   maxpool  per (document, dimension): pooled = -inf, replaced only when pooled < token[i] (std::max: a NaN never enters); a
+ *            non-finite result becomes 0.0f; an empty document gives zeros.  Then norm = sqrt of ONE fp64 chain of
+ *            double(v) * double(v) in element order (exact products: form-free); norm > 1e-8: v = float(double(v) / norm),
+ *            otherwise a row of zeros.
+ * Results equal the CPU loop bit for bit in the form asked for; a NaN score is some NaN (x86 and the device give the default
+ * NaN different signs).  Documents are CSR over one row pool: doc_offsets [n_docs + 1] uint64 from 0, never decreasing.
+ * Limits: dim <= YAMS_RERANK_MAX_DIM, tq <= YAMS_RERANK_MAX_QUERY_TOKENS, n_docs <= YAMS_RERANK_MAX_DOCS, n_docs * tq <=
+ * YAMS_RERANK_MAX_ROWMAX, a document <= YAMS_RERANK_MAX_DOC_TOKENS rows, the pool <= YAMS_RERANK_MAX_ROWS rows: beyond,
+ * YAMS_ERR_UNSUPPORTED.  dim == 0, a null array that is needed, offsets that do not start at 0 or decrease, an unknown form, an
+ * output overlapping an input: YAMS_ERR_INVALID_ARG.  Every refusal is found before anything is written.  Every call
+ * synchronises the context's stream before returning.  The _host twins take host arrays throughout. */
+#define YAMS_RERANK_MAX_DIM 1024u
+#define YAMS_RERANK_MAX_DOC_TOKENS (1u << 20)
+#define YAMS_RERANK_MAX_QUERY_TOKENS (1u << 16)
+#define YAMS_RERANK_MAX_ROWS (1ull << 28)
+#define YAMS_RERANK_MAX_DOCS (1ull << 20)
+#define YAMS_RERANK_MAX_ROWMAX (1ull << 27)
+#define YAMS_RERANK_PATH_VALU 0u /* register tiles of chains on the vector ALU */
+#define YAMS_RERANK_PATH_MFMA 1u /* v_mfma_f32_32x32x2_f32: the fused form only */
+#define YAMS_RERANK_NONE 0xffffffffu /* out_rowarg: no token won, the row maximum is the initial -inf */
+typedef struct yams_rerank_diag {
+    uint32_t path;         /* YAMS_RERANK_PATH_* that served the chains */
+    uint32_t form;         /* the form asked for */
+    uint64_t rows;         /* document token rows seen (the last offset) */
+    uint64_t docs;         /* documents seen */
+    uint32_t query_tokens; /* query tokens seen */
+    uint32_t reserved;
+} yams_rerank_diag_t;
+/* computeMaxSim(query, document) of every document of the window at once.
+ *   query        [tq][dim] fp32       rows  [doc_offsets[n_docs]][dim] fp32: the documents' token rows
+ *   out_scores   [n_docs] fp32
+ *   out_rowmax   nullable, [n_docs][tq] fp32: maxSim of every (document, query token)
+ *   out_rowarg   nullable, [n_docs][tq] uint32, written only along with out_rowmax: the token (index inside its document) whose
+ *                sim stayed, YAMS_RERANK_NONE where none did
+ *   diag         nullable, written on YAMS_OK
+ * n_docs == 0: YAMS_OK, nothing written. */
+YAMS_ACCEL_API yams_status_t yams_rerank_maxsim_device(
+    yams_accel_ctx* ctx, const float* query, uint32_t tq, uint32_t dim, const float* rows, const uint64_t* doc_offsets,
+    uint64_t n_docs, uint32_t form, float* out_scores, float* out_rowmax, uint32_t* out_rowarg, yams_rerank_diag_t* diag);
+YAMS_ACCEL_API yams_status_t yams_rerank_maxsim_host(
+    yams_accel_ctx* ctx, const float* query, uint32_t tq, uint32_t dim, const float* rows, const uint64_t* doc_offsets,
+    uint64_t n_docs, uint32_t form, float* out_scores, float* out_rowmax, uint32_t* out_rowarg, yams_rerank_diag_t* diag);
+/* normalizeEmbedding(maxPoolEmbeddings(document, dim)) of every document at once.  out [n_docs][dim] fp32.
+ * n_docs == 0: YAMS_OK, nothing written. */
+YAMS_ACCEL_API yams_status_t yams_rerank_maxpool_device(
+    yams_accel_ctx* ctx, const float* rows, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, float* out);
+YAMS_ACCEL_API yams_status_t yams_rerank_maxpool_host(
+    yams_accel_ctx* ctx, const float* rows, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, float* out);
+
+/* ------------------------------------------------------------------------------------------ */
 /* The semantic-neighbour graph: exact top-K self-join of the document-level embeddings         */
 /* ------------------------------------------------------------------------------------------ */
 /* EmbeddingService::updateSemanticNeighborGraphUnlocked (src/daemon/components/EmbeddingService.cpp) scores, for every
@@ -1752,6 +1817,23 @@ typedef struct yams_topology_features_v1 {
                              uint32_t k, const uint8_t* entity_on, const uint32_t* sig, uint32_t sig_len, const uint8_t* sketch_on,
                              uint32_t sketch_dim, float alpha_e, float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims);
 } yams_topology_features_v1;
+
+/* The late-interaction rerank (yams_rerank_maxsim_host / yams_rerank_maxpool_host) for a host that holds the token embeddings in
+ * its own memory.  A separate interface, version 1, served by yams_plugin_get_interface and NOT listed in the manifest, for the
+ * reason given at vector_doc_scan_v1.  Host memory in, host memory out: every output is the caller's array.  Statuses and
+ * limits of the flat entries. */
+#define YAMS_IFACE_LATE_INTERACTION_RERANK_V1 "late_interaction_rerank_v1"
+#define YAMS_IFACE_LATE_INTERACTION_RERANK_V1_VERSION 1u
+typedef struct yams_late_interaction_rerank_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_LATE_INTERACTION_RERANK_V1_VERSION */
+    void* self;
+    /* out_scores: the caller's [n_docs]; out_rowmax / out_rowarg: nullable, the caller's [n_docs][tq]; diag: nullable */
+    yams_status_t (*maxsim)(void* self, const float* query, uint32_t tq, uint32_t dim, const float* rows, const uint64_t* doc_offsets,
+                            uint64_t n_docs, uint32_t form, float* out_scores, float* out_rowmax, uint32_t* out_rowarg,
+                            yams_rerank_diag_t* diag);
+    /* out: the caller's [n_docs][dim] */
+    yams_status_t (*maxpool)(void* self, const float* rows, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, float* out);
+} yams_late_interaction_rerank_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

@@ -316,6 +316,31 @@ class TopologyFeaturesV1(C.Structure):  # topology_features_v1 (served by get_in
     ]
 
 
+# YAMS_RERANK_MAX_* / YAMS_RERANK_PATH_* / YAMS_RERANK_NONE
+RERANK_MAX_DIM, RERANK_MAX_DOC_TOKENS, RERANK_MAX_QUERY_TOKENS = 1024, 1 << 20, 1 << 16
+RERANK_MAX_ROWS, RERANK_MAX_DOCS, RERANK_MAX_ROWMAX = 1 << 28, 1 << 20, 1 << 27
+RERANK_PATH_VALU, RERANK_PATH_MFMA, RERANK_NONE = 0, 1, 0xFFFFFFFF
+RERANK_Q_TILE, RERANK_D_TILE, RERANK_K_CHUNK = 32, 256, 32     # rerank_launch.h: the kernel's tiles (the tests' lattice)
+IFACE_LATE_INTERACTION_RERANK_V1 = "late_interaction_rerank_v1"
+
+
+class RerankDiag(C.Structure):  # yams_rerank_diag_t
+    _fields_ = [("path", C.c_uint32), ("form", C.c_uint32), ("rows", C.c_uint64), ("docs", C.c_uint64),
+                ("query_tokens", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_RERANK_MAXSIM = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.POINTER(RerankDiag)]
+_RERANK_MAXPOOL = [vp, C.c_uint32, vp, C.c_uint64, vp]
+
+
+class LateInteractionRerankV1(C.Structure):  # late_interaction_rerank_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("maxsim", C.CFUNCTYPE(C.c_int, vp, *_RERANK_MAXSIM)),
+        ("maxpool", C.CFUNCTYPE(C.c_int, vp, *_RERANK_MAXPOOL)),
+    ]
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -392,6 +417,7 @@ EXPORTS = [
     "yams_quality_persistence_h0_device", "yams_quality_persistence_h0_host",
     "yams_features_aggregate_device", "yams_features_aggregate_host", "yams_features_variance_device", "yams_features_variance_host",
     "yams_features_compose_device", "yams_features_compose_host",
+    "yams_rerank_maxsim_device", "yams_rerank_maxsim_host", "yams_rerank_maxpool_device", "yams_rerank_maxpool_host",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -508,6 +534,10 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
         fn.argtypes = [vp, *_FEATURES_VARIANCE]
     for fn in (L.yams_features_compose_device, L.yams_features_compose_host):
         fn.argtypes = [vp, *_FEATURES_COMPOSE]
+    for fn in (L.yams_rerank_maxsim_device, L.yams_rerank_maxsim_host):
+        fn.argtypes = [vp, *_RERANK_MAXSIM]
+    for fn in (L.yams_rerank_maxpool_device, L.yams_rerank_maxpool_host):
+        fn.argtypes = [vp, *_RERANK_MAXPOOL]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

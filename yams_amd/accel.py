@@ -897,6 +897,41 @@ class Accel:
                           alpha_m, o[0], out_stride, o[1]), misalign)
         return out.reshape(n, out_stride), dims
 
+    # ---- late-interaction rerank (yams_rerank_*) ----------------------------------------------------------------------------------
+    def rerank_maxsim(self, query: np.ndarray, rows: np.ndarray, doc_offsets, form: int = _lib.RESIDUAL_SEPARATE, want_rowmax: bool = False,
+                      host_entry: bool = False, misalign: int = 0):
+        """computeMaxSim of every document of a window (yams_rerank_maxsim_device / _host): query [tq][dim] float32, rows
+        [total][dim] float32, CSR documents.  Returns (scores [n_docs] float32, diag dict) or, with want_rowmax, (scores, rowmax
+        [n_docs][tq] float32, rowarg [n_docs][tq] uint32, diag)."""
+        q = np.ascontiguousarray(query, np.float32)
+        x = np.ascontiguousarray(rows, np.float32)
+        tq, dim = q.shape
+        off = np.ascontiguousarray(doc_offsets, np.uint64)
+        d = len(off) - 1
+        dg = _lib.RerankDiag()
+        outs = [(np.float32, d), (np.float32, d * tq) if want_rowmax else None, (np.uint32, d * tq) if want_rowmax else None]
+        sc, mx, arg = self._artifact_call(
+            self.L.yams_rerank_maxsim_device, self.L.yams_rerank_maxsim_host, host_entry,
+            [q if q.size else None, x if x.size else None, off], outs,
+            lambda i, o: (i[0], tq, dim, i[1], i[2], d, form, o[0], o[1], o[2], C.byref(dg)), misalign)
+        diag = {k: getattr(dg, k) for k, _ in _lib.RerankDiag._fields_}
+        if want_rowmax:
+            return sc, mx.reshape(d, tq), arg.reshape(d, tq), diag
+        return sc, diag
+
+    def rerank_maxpool(self, rows: np.ndarray, doc_offsets, host_entry: bool = False, misalign: int = 0):
+        """normalizeEmbedding(maxPoolEmbeddings(document)) of every document (yams_rerank_maxpool_device / _host).  Returns out
+        [n_docs][dim] float32."""
+        x = np.ascontiguousarray(rows, np.float32)
+        dim = x.shape[1]
+        off = np.ascontiguousarray(doc_offsets, np.uint64)
+        d = len(off) - 1
+        out, = self._artifact_call(
+            self.L.yams_rerank_maxpool_device, self.L.yams_rerank_maxpool_host, host_entry,
+            [x if x.size else None, off], [(np.float32, d * dim)],
+            lambda i, o: (i[0], dim, i[1], d, o[0]), misalign)
+        return out.reshape(d, dim)
+
     # ---- cluster routing (yams_route_index_* / yams_route_dense_*) ----------------------------------------------------------
     def route_index(self, vectors: np.ndarray, cluster_offsets, has_centroid, position, host_entry: bool = False,
                     misalign: int = 0) -> "RouteIndex":

@@ -1,8 +1,8 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// thirteen interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, topology_quality_v1, topology_features_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
+// fourteen interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
+// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, topology_quality_v1, topology_features_v1, late_interaction_rerank_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
@@ -1494,6 +1494,22 @@ yams_status_t tf_compose(void*, const float* dense, uint64_t n, uint32_t dim, co
 yams_topology_features_v1 g_topology_features = {YAMS_IFACE_TOPOLOGY_FEATURES_V1_VERSION, nullptr, GUARDED(tf_aggregate), GUARDED(tf_variance),
                                                  GUARDED(tf_compose)};
 
+// ---- late_interaction_rerank_v1: ColBERT MaxSim and token pooling over host memory (yams_rerank_*_host) ----------------------
+// every output is the caller's array: every check is the flat entry's
+yams_status_t lr_maxsim(void*, const float* query, uint32_t tq, uint32_t dim, const float* rows, const uint64_t* doc_offsets, uint64_t n_docs,
+                        uint32_t form, float* out_scores, float* out_rowmax, uint32_t* out_rowarg, yams_rerank_diag_t* diag) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    return yams_rerank_maxsim_host(lease.v, query, tq, dim, rows, doc_offsets, n_docs, form, out_scores, out_rowmax, out_rowarg, diag);
+}
+yams_status_t lr_maxpool(void*, const float* rows, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, float* out) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    return yams_rerank_maxpool_host(lease.v, rows, dim, doc_offsets, n_docs, out);
+}
+
+yams_late_interaction_rerank_v1 g_late_rerank = {YAMS_IFACE_LATE_INTERACTION_RERANK_V1_VERSION, nullptr, GUARDED(lr_maxsim), GUARDED(lr_maxpool)};
+
 // ---- content_checksum_v1: the compressed store's CRC-32 over host memory (yams_crc32_many_host) ------------------------------
 yams_status_t cs_crc32_many(void*, const uint8_t* const* msgs, const size_t* lens, size_t n, uint32_t* out) {
     NEED_INIT();
@@ -1778,6 +1794,7 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
         {YAMS_IFACE_TOPOLOGY_ROUTE_V1, YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION, &g_topology_route},
         {YAMS_IFACE_TOPOLOGY_QUALITY_V1, YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION, &g_topology_quality},
         {YAMS_IFACE_TOPOLOGY_FEATURES_V1, YAMS_IFACE_TOPOLOGY_FEATURES_V1_VERSION, &g_topology_features},
+        {YAMS_IFACE_LATE_INTERACTION_RERANK_V1, YAMS_IFACE_LATE_INTERACTION_RERANK_V1_VERSION, &g_late_rerank},
         {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
         {YAMS_IFACE_CONTENT_CHECKSUM_V1, YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, &g_content_checksum},
         {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};

@@ -1,0 +1,224 @@
+// rerank_api.cpp — yams_rerank_maxsim / yams_rerank_maxpool (_device and _host): OnnxColbertSession's computeMaxSim over a
+// window of candidate documents, and maxPoolEmbeddings + normalizeEmbedding, behind the C ABI.  Every entry: the limits (no
+// device needed) -> argument checks -> the pool's total read back -> ONE read-back of the check flags -> the work.  Nothing is
+// written to an output before every refusal is known.
+#include <cstdlib>
+#include <cstring>
+
+#include "accel_ctx.h"
+#include "rerank_launch.h"
+
+using namespace yams_accel;
+
+namespace {
+
+static_assert(YAMS_RERANK_MAX_DIM == kRerankMaxDim && YAMS_RERANK_MAX_DOC_TOKENS == kRerankMaxDocTokens &&
+                  YAMS_RERANK_MAX_QUERY_TOKENS == kRerankMaxQueryTokens && YAMS_RERANK_MAX_ROWS == kRerankMaxRows &&
+                  YAMS_RERANK_MAX_DOCS == kRerankMaxDocs && YAMS_RERANK_MAX_ROWMAX == kRerankMaxRowMax,
+              "the header's limits are the launchers'");
+static_assert(YAMS_RERANK_PATH_VALU == kRerankValu && YAMS_RERANK_PATH_MFMA == kRerankMfma, "the diag's path is the launcher's");
+
+bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    if (!a || !b || !a_bytes || !b_bytes) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+RerankPath fused_path() {
+#ifdef YAMS_ACCEL_MEASURE
+    if (const char* e = std::getenv("YAMS_ACCEL_RERANK_FUSED_PATH")) return std::strcmp(e, "valu") == 0 ? kRerankValu : kRerankMfma;
+#endif
+    return kRerankFusedPath;
+}
+
+// what needs no device
+yams_status_t check_maxsim(yams_accel_ctx* ctx, const float* query, uint32_t tq, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs,
+                           uint32_t form, const float* out_scores) {
+    if (dim > YAMS_RERANK_MAX_DIM) return fail(ctx, YAMS_ERR_UNSUPPORTED, "dim exceeds YAMS_RERANK_MAX_DIM");
+    if (tq > YAMS_RERANK_MAX_QUERY_TOKENS) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the query exceeds YAMS_RERANK_MAX_QUERY_TOKENS");
+    if (n_docs > YAMS_RERANK_MAX_DOCS) return fail(ctx, YAMS_ERR_UNSUPPORTED, "n_docs exceeds YAMS_RERANK_MAX_DOCS");
+    if (n_docs * tq > YAMS_RERANK_MAX_ROWMAX) return fail(ctx, YAMS_ERR_UNSUPPORTED, "n_docs * query tokens exceeds YAMS_RERANK_MAX_ROWMAX");
+    if (dim == 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "dim == 0");
+    if (form != YAMS_RESIDUAL_SEPARATE && form != YAMS_RESIDUAL_FUSED) return fail(ctx, YAMS_ERR_INVALID_ARG, "unknown form");
+    if (n_docs && (!doc_offsets || !out_scores)) return fail(ctx, YAMS_ERR_INVALID_ARG, "null doc_offsets or out_scores");
+    if (n_docs && tq && !query) return fail(ctx, YAMS_ERR_INVALID_ARG, "null query");
+    return YAMS_OK;
+}
+// once the pool's total is known
+yams_status_t check_maxsim_total(yams_accel_ctx* ctx, const float* query, uint32_t tq, uint32_t dim, const float* rows, uint64_t total,
+                                 uint64_t n_docs, const float* out_scores, const float* out_rowmax) {
+    if (total > YAMS_RERANK_MAX_ROWS) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the row pool exceeds YAMS_RERANK_MAX_ROWS");
+    if (total && !rows) return fail(ctx, YAMS_ERR_INVALID_ARG, "null rows");
+    const size_t rb = static_cast<size_t>(total) * dim * 4, qb = static_cast<size_t>(tq) * dim * 4, sb = static_cast<size_t>(n_docs) * 4,
+                 mb = static_cast<size_t>(n_docs) * tq * 4;
+    if (overlaps(out_scores, sb, rows, rb) || overlaps(out_scores, sb, query, qb) || overlaps(out_rowmax, mb, rows, rb) ||
+        overlaps(out_rowmax, mb, query, qb) || overlaps(out_scores, sb, out_rowmax, mb))
+        return fail(ctx, YAMS_ERR_INVALID_ARG, "an output overlaps an input or the other output");
+    return YAMS_OK;
+}
+
+yams_status_t check_maxpool(yams_accel_ctx* ctx, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, const float* out) {
+    if (dim > YAMS_RERANK_MAX_DIM) return fail(ctx, YAMS_ERR_UNSUPPORTED, "dim exceeds YAMS_RERANK_MAX_DIM");
+    if (n_docs > YAMS_RERANK_MAX_DOCS) return fail(ctx, YAMS_ERR_UNSUPPORTED, "n_docs exceeds YAMS_RERANK_MAX_DOCS");
+    if (dim == 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "dim == 0");
+    if (n_docs && (!doc_offsets || !out)) return fail(ctx, YAMS_ERR_INVALID_ARG, "null doc_offsets or out");
+    return YAMS_OK;
+}
+yams_status_t check_maxpool_total(yams_accel_ctx* ctx, uint32_t dim, const float* rows, uint64_t total, uint64_t n_docs, const float* out) {
+    if (total > YAMS_RERANK_MAX_ROWS) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the row pool exceeds YAMS_RERANK_MAX_ROWS");
+    if (total && !rows) return fail(ctx, YAMS_ERR_INVALID_ARG, "null rows");
+    if (overlaps(out, static_cast<size_t>(n_docs) * dim * 4, rows, static_cast<size_t>(total) * dim * 4))
+        return fail(ctx, YAMS_ERR_INVALID_ARG, "out overlaps rows");
+    return YAMS_OK;
+}
+
+// the offsets as the host sees them; the same verdicts as the device check
+yams_status_t check_offsets_host(yams_accel_ctx* ctx, const uint64_t* off, uint64_t n_docs) {
+    if (off[0] != 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+    for (uint64_t i = 0; i < n_docs; ++i) {
+        if (off[i + 1] < off[i]) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+        if (off[i + 1] - off[i] > YAMS_RERANK_MAX_DOC_TOKENS) return fail(ctx, YAMS_ERR_UNSUPPORTED, "a document exceeds YAMS_RERANK_MAX_DOC_TOKENS");
+    }
+    return YAMS_OK;
+}
+
+// The pool's total (the last offset) and the offsets' checks, over device offsets.  Synchronises.
+yams_status_t device_total(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t n_docs, uint64_t* total) {
+    hipStream_t st = ctx->stream;
+    uint64_t* h_total;
+    YA_TRY(pinned_get(ctx, 64, (void**)&h_total));
+    YA_HIP(ctx, hipMemcpyAsync(h_total, d_off + n_docs, 8, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    *total = *h_total;
+    return YAMS_OK;
+}
+yams_status_t device_check(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t n_docs, uint64_t total) {
+    hipStream_t st = ctx->stream;
+    uint32_t* d_flags; uint32_t* h_flags;
+    YA_TRY(ws_get(ctx, "rerank_flags", 16, (void**)&d_flags));
+    YA_TRY(pinned_get(ctx, 64, (void**)&h_flags));
+    YA_HIP(ctx, hipMemsetAsync(d_flags, 0, 16, st));
+    YA_HIP(ctx, launch_rerank_check(st, d_off, n_docs, total, YAMS_RERANK_MAX_DOC_TOKENS, d_flags));
+    YA_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, 4, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    if (*h_flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+    if (*h_flags & 2u) return fail(ctx, YAMS_ERR_UNSUPPORTED, "a document exceeds YAMS_RERANK_MAX_DOC_TOKENS");
+    return YAMS_OK;
+}
+
+} // namespace
+
+// ---- MaxSim ------------------------------------------------------------------------------------------------------------------
+extern "C" yams_status_t yams_rerank_maxsim_device(yams_accel_ctx* ctx, const float* query, uint32_t tq, uint32_t dim, const float* rows,
+                                                   const uint64_t* doc_offsets, uint64_t n_docs, uint32_t form, float* out_scores,
+                                                   float* out_rowmax, uint32_t* out_rowarg, yams_rerank_diag_t* diag) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    YA_TRY(check_maxsim(ctx, query, tq, dim, doc_offsets, n_docs, form, out_scores));
+    if (n_docs == 0) return YAMS_OK;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    uint64_t total;
+    YA_TRY(device_total(ctx, doc_offsets, n_docs, &total));
+    YA_TRY(check_maxsim_total(ctx, query, tq, dim, rows, total, n_docs, out_scores, out_rowmax));
+    YA_TRY(device_check(ctx, doc_offsets, n_docs, total));
+    const bool fused = form == YAMS_RESIDUAL_FUSED;
+    const RerankPath path = fused ? fused_path() : kRerankValu;
+    float* d_rowmax = out_rowmax;
+    if (!d_rowmax && tq) YA_TRY(ws_get(ctx, "rerank_rowmax", static_cast<size_t>(n_docs) * tq * 4, (void**)&d_rowmax));
+    {
+        TimedRegion tr(ctx, "rerank_maxsim");
+        hipError_t e = launch_rerank_rowmax(st, query, tq, dim, rows, doc_offsets, static_cast<uint32_t>(n_docs), fused, path, d_rowmax,
+                                            out_rowmax ? out_rowarg : nullptr);
+        if (e == hipSuccess) e = launch_rerank_score(st, d_rowmax, tq, static_cast<uint32_t>(n_docs), out_scores);
+        tr.end();
+        YA_HIP(ctx, e);
+    }
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    if (diag) {
+        diag->path = path;
+        diag->form = form;
+        diag->rows = total;
+        diag->docs = n_docs;
+        diag->query_tokens = tq;
+        diag->reserved = 0;
+    }
+    return YAMS_OK;
+}
+
+extern "C" yams_status_t yams_rerank_maxsim_host(yams_accel_ctx* ctx, const float* query, uint32_t tq, uint32_t dim, const float* rows,
+                                                 const uint64_t* doc_offsets, uint64_t n_docs, uint32_t form, float* out_scores,
+                                                 float* out_rowmax, uint32_t* out_rowarg, yams_rerank_diag_t* diag) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    YA_TRY(check_maxsim(ctx, query, tq, dim, doc_offsets, n_docs, form, out_scores));
+    if (n_docs == 0) return YAMS_OK;
+    YA_TRY(check_offsets_host(ctx, doc_offsets, n_docs));      // judged here, before an upload is sized by them
+    const uint64_t total = doc_offsets[n_docs];
+    YA_TRY(check_maxsim_total(ctx, query, tq, dim, rows, total, n_docs, out_scores, out_rowmax));
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t rb = static_cast<size_t>(total) * dim * 4, qb = static_cast<size_t>(tq) * dim * 4, sb = static_cast<size_t>(n_docs) * 4,
+                 mb = static_cast<size_t>(n_docs) * tq * 4;
+    const bool want_max = out_rowmax && mb, want_arg = want_max && out_rowarg;
+    float* d_q; float* d_rows; uint64_t* d_off; float* d_scores; float* d_max = nullptr; uint32_t* d_arg = nullptr;
+    YA_TRY(ws_get(ctx, "rerank_host_query", qb + 16, (void**)&d_q));
+    YA_TRY(ws_get(ctx, "rerank_host_rows", rb + 16, (void**)&d_rows));
+    YA_TRY(ws_get(ctx, "rerank_host_offsets", (static_cast<size_t>(n_docs) + 1) * 8, (void**)&d_off));
+    YA_TRY(ws_get(ctx, "rerank_host_scores", sb, (void**)&d_scores));
+    if (want_max) YA_TRY(ws_get(ctx, "rerank_host_rowmax", mb, (void**)&d_max));
+    if (want_arg) YA_TRY(ws_get(ctx, "rerank_host_rowarg", mb, (void**)&d_arg));
+    if (qb) YA_HIP(ctx, staged_h2d(d_q, query, qb, st));
+    if (rb) YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
+    YA_HIP(ctx, staged_h2d(d_off, doc_offsets, (static_cast<size_t>(n_docs) + 1) * 8, st));
+    yams_rerank_diag_t dg{};
+    YA_TRY(yams_rerank_maxsim_device(ctx, d_q, tq, dim, d_rows, d_off, n_docs, form, d_scores, d_max, d_arg, &dg));
+    YA_HIP(ctx, hipMemcpyAsync(out_scores, d_scores, sb, hipMemcpyDeviceToHost, st));
+    if (want_max) YA_HIP(ctx, hipMemcpyAsync(out_rowmax, d_max, mb, hipMemcpyDeviceToHost, st));
+    if (want_arg) YA_HIP(ctx, hipMemcpyAsync(out_rowarg, d_arg, mb, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    if (diag) *diag = dg;
+    return YAMS_OK;
+}
+
+// ---- max-pool + L2 normalisation ---------------------------------------------------------------------------------------------
+extern "C" yams_status_t yams_rerank_maxpool_device(yams_accel_ctx* ctx, const float* rows, uint32_t dim, const uint64_t* doc_offsets,
+                                                    uint64_t n_docs, float* out) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    YA_TRY(check_maxpool(ctx, dim, doc_offsets, n_docs, out));
+    if (n_docs == 0) return YAMS_OK;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    uint64_t total;
+    YA_TRY(device_total(ctx, doc_offsets, n_docs, &total));
+    YA_TRY(check_maxpool_total(ctx, dim, rows, total, n_docs, out));
+    YA_TRY(device_check(ctx, doc_offsets, n_docs, total));
+    {
+        TimedRegion tr(ctx, "rerank_maxpool");
+        YA_HIP(ctx, launch_rerank_maxpool(st, rows, dim, doc_offsets, static_cast<uint32_t>(n_docs), out));
+        tr.end();
+    }
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    return YAMS_OK;
+}
+
+extern "C" yams_status_t yams_rerank_maxpool_host(yams_accel_ctx* ctx, const float* rows, uint32_t dim, const uint64_t* doc_offsets,
+                                                  uint64_t n_docs, float* out) {
+    if (!ctx) return YAMS_ERR_INVALID_ARG;
+    YA_TRY(check_maxpool(ctx, dim, doc_offsets, n_docs, out));
+    if (n_docs == 0) return YAMS_OK;
+    YA_TRY(check_offsets_host(ctx, doc_offsets, n_docs));
+    const uint64_t total = doc_offsets[n_docs];
+    YA_TRY(check_maxpool_total(ctx, dim, rows, total, n_docs, out));
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t rb = static_cast<size_t>(total) * dim * 4, ob = static_cast<size_t>(n_docs) * dim * 4;
+    float* d_rows; uint64_t* d_off; float* d_out;
+    YA_TRY(ws_get(ctx, "rerank_host_rows", rb + 16, (void**)&d_rows));
+    YA_TRY(ws_get(ctx, "rerank_host_offsets", (static_cast<size_t>(n_docs) + 1) * 8, (void**)&d_off));
+    YA_TRY(ws_get(ctx, "rerank_host_pooled", ob, (void**)&d_out));
+    if (rb) YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
+    YA_HIP(ctx, staged_h2d(d_off, doc_offsets, (static_cast<size_t>(n_docs) + 1) * 8, st));
+    YA_TRY(yams_rerank_maxpool_device(ctx, d_rows, dim, d_off, n_docs, d_out));
+    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
+    YA_HIP(ctx, hipStreamSynchronize(st));
+    return YAMS_OK;
+}
