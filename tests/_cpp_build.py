@@ -125,3 +125,21 @@ def build_plugin_host_test():
     if r.returncode != 0:
         raise RuntimeError("plugin_host_test failed to compile:\n" + r.stdout.decode())
     return exe
+
+
+def build_arg_checks_test():
+    """Compiles tests/cpp/arg_checks_test.cpp (plain g++, no GPU, no ROCm include path: yams_amd/csrc/arg_checks.h is pure host
+    code) with AddressSanitizer and UBSan, as build_plugin_host_test does.  Returns the executable."""
+    out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "arg_checks_test")
+    src = os.path.join(ROOT, "tests", "cpp", "arg_checks_test.cpp")
+    deps = [src, os.path.join(ROOT, "yams_amd", "csrc", "arg_checks.h")]
+    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
+        return exe
+    r = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra",
+                        "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    if r.returncode != 0:
+        raise RuntimeError("arg_checks_test failed to compile:\n" + r.stdout.decode())
+    return exe

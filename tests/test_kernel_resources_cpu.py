@@ -6,55 +6,13 @@ dominant kernel family — must not use scratch at all."""
 import os
 import re
 import shutil
-import subprocess
-import tempfile
 
 import pytest
 
+from _kernel_asm import kernel_asm
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def _assembly(src):
-    """The gfx950 assembly (lines) of the product build of one translation unit."""
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "k.s")
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
-               "--cuda-device-only", "-S", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "yams_amd", "csrc"),
-               os.path.join(ROOT, "yams_amd", "csrc", src), "-o", out]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-        assert r.returncode == 0, r.stdout[-3000:]
-        return open(out).read().splitlines()
-
-
-def _kernels(src, text=None):
-    """{mangled kernel name: [assembly lines]} of the product build of one translation unit."""
-    kernels, cur = {}, None
-    for line in text if text is not None else _assembly(src):
-        m = re.match(r"^(_ZN10yams_accel\w+):", line)
-        if m:
-            cur = m.group(1); kernels[cur] = []
-        elif cur is not None:
-            kernels[cur].append(line)
-            if "s_endpgm" in line:
-                cur = None
-    return kernels
-
-
-def _metadata(text):
-    """{mangled kernel name: {key: int}} of the integer fields of the amdhsa.kernels metadata the assembly carries."""
-    meta, cur = {}, None
-    for line in text:
-        if line.startswith("  - ."):
-            cur = {}
-        m = re.match(r"^(?:  - |    )\.(\w+):\s+(\S+)$", line)
-        if cur is None or not m:
-            continue
-        if m.group(1) == "name":
-            meta[m.group(2)] = cur
-        elif m.group(2).isdigit():
-            cur[m.group(1)] = int(m.group(2))
-    return meta
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
@@ -68,9 +26,8 @@ def test_the_fp64_tile_kernels_keep_three_waves_their_lds_and_no_scratch(src, ke
     scratch_ instruction) and the static LDS of the two operand buffers (+ 64 bytes of counters in the pairs kernel).
     sgpr_spills = (vector form, scalar form): scalar registers parked in lanes of a vector register, never in memory; the
     scalar-load form of the pairs kernel has had six since it was written, the other three forms none."""
-    text = _assembly(src)
-    meta = {k: v for k, v in _metadata(text).items() if kernel in k}
-    bodies = {k: v for k, v in _kernels(src, text).items() if kernel in k}
+    meta = {k: v for k, v in kernel_asm(src).meta.items() if kernel in k}
+    bodies = {k: v for k, v in kernel_asm(src).kernels.items() if kernel in k}
     assert len(meta) == 2 and set(meta) == set(bodies), (list(meta), list(bodies))
     assert {("ILb1E" in k) for k in meta} == {True, False}, list(meta)       # <VEC = true> and <VEC = false>
     for name, m in meta.items():
@@ -98,7 +55,7 @@ def test_the_row_chain_kernels_keep_their_waves_their_lds_and_no_scratch(src, ke
     header = open(os.path.join(ROOT, "yams_amd", "csrc", "row_chains.h")).read()
     c = {k: int(v) for k, v in re.findall(r"constexpr\s+int\s+(kRow\w+)\s*=\s*(\d+)\s*;", header)}
     assert {"kRowThreads", "kRowChunk"} <= set(c), c      # (the row stride is the chunk padded by one float: the LDS figure below)
-    meta = {k: v for k, v in _metadata(_assembly(src)).items() if kernel in k}
+    meta = {k: v for k, v in kernel_asm(src).meta.items() if kernel in k}
     assert len(meta) == 3, list(meta)
     for qg, w in waves.items():
         name = [k for k in meta if "%sILi%dEE" % (kernel, qg) in k]
@@ -113,7 +70,7 @@ def test_the_row_chain_kernels_keep_their_waves_their_lds_and_no_scratch(src, ke
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
 @pytest.mark.parametrize("src", ["scan_i8_kernel.hip", "scan_bf16_kernel.hip"])
 def test_no_scratch_traffic_inside_the_mfma_loops(src):
-    tiles = {k: v for k, v in _kernels(src).items() if "scan_tiles" in k}
+    tiles = {k: v for k, v in kernel_asm(src).kernels.items() if "scan_tiles" in k}
     assert tiles
     for name, body in tiles.items():
         mf = [i for i, l in enumerate(body) if "v_mfma" in l]
@@ -136,7 +93,7 @@ def test_direct_row_loads_are_not_touched_while_in_flight():
     slab makes them valid.  Nothing the compiler puts in between — a copy at a loop edge, a spill, a reuse — may read or
     write those registers: checked on the assembly in program order (a linear walk; the kernel's loops are the unrolled
     slab pairs, so program order is what matters between a load and its wait)."""
-    kernels = {k: v for k, v in _kernels("scan_i8_kernel.hip").items() if "scan_tiles_i8r_kernel" in k and "ELb1ELi" in k}   # <ABL, L2, DIRECT = true, ZSM>
+    kernels = {k: v for k, v in kernel_asm("scan_i8_kernel.hip").kernels.items() if "scan_tiles_i8r_kernel" in k and "ELb1ELi" in k}   # <ABL, L2, DIRECT = true, ZSM>
     assert len(kernels) == 3, list(kernels)      # the cosine filter, the L2 filter, the cosine SAMPLE pass
 
     def regs(tok):
@@ -182,7 +139,7 @@ def test_deep_form_row_loads_are_not_touched_while_in_flight():
     still have a load due: nothing may read or write them — not a copy, not a spill, not a temporary the allocator parks
     there (round 6: the flush after the last strip did exactly that and stored through an overwritten address; a bus error
     on shards of 4M rows and more).  The kernel must not use scratch at all."""
-    kernels = {k: v for k, v in _kernels("scan_i8_kernel.hip").items() if "scan_tiles_i8d_kernel" in k}
+    kernels = {k: v for k, v in kernel_asm("scan_i8_kernel.hip").kernels.items() if "scan_tiles_i8d_kernel" in k}
     assert len(kernels) == 1, list(kernels)
 
     def regs(tok):

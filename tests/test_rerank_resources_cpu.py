@@ -7,10 +7,10 @@ other f32 arithmetic; no float atomics anywhere."""
 import os
 import re
 import shutil
-import subprocess
-import tempfile
 
 import pytest
+
+from _kernel_asm import kernel_asm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -27,30 +27,7 @@ MFMA = re.compile(r"\bv_mfma_f32_32x32x2_f32")
 def assembly():
     if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
         pytest.fail("hipcc is needed to compile rerank_kernels.hip")
-    from yams_amd import build as b
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "k.s")
-        cmd = [HIPCC, *[f for f in b.FLAGS if f not in ("-x", "hip")], "-x", "hip", "--cuda-device-only", "-S",
-               os.path.join(ROOT, "yams_amd", "csrc", "rerank_kernels.hip"), "-o", out]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-        assert r.returncode == 0, r.stdout[-3000:]
-        text = open(out).read()
-    kernels, cur = {}, None
-    for line in text.splitlines():
-        m = re.match(r"^(_ZN10yams_accel\w+):", line)
-        if m:
-            cur = m.group(1); kernels[cur] = []
-        elif cur is not None:
-            if line.startswith(".Lfunc_end"):
-                cur = None
-            else:
-                kernels[cur].append(line.split(";")[0])
-    meta = {}
-    for block in text.split("  - .")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block)
-        if name:
-            meta[name.group(1)] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", block, re.M)}
-    return kernels, meta, text
+    return kernel_asm("rerank_kernels.hip")
 
 
 def named(table, part):

@@ -4,10 +4,10 @@ fused into them, and the products are fp64 multiplies; no kernel of the file use
 import os
 import re
 import shutil
-import subprocess
-import tempfile
 
 import pytest
+
+from _kernel_asm import kernel_asm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -18,24 +18,7 @@ FORMS = {"vector loads": "sgc_hop_kernelILi4ELb1ELb0E", "element loads": "sgc_ho
 def assembly():
     if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
         pytest.fail("hipcc is needed to compile sgc_kernels.hip")
-    from yams_amd import build as b
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "k.s")
-        cmd = [HIPCC, *[f for f in b.FLAGS if f not in ("-x", "hip")], "-x", "hip", "--cuda-device-only", "-S",
-               os.path.join(ROOT, "yams_amd", "csrc", "sgc_kernels.hip"), "-o", out]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-        assert r.returncode == 0, r.stdout[-3000:]
-        text = open(out).read()
-    kernels, cur = {}, None
-    for line in text.splitlines():
-        m = re.match(r"^(_ZN10yams_accel\w+):", line)
-        if m:
-            cur = m.group(1); kernels[cur] = []
-        elif cur is not None:
-            if line.startswith(".Lfunc_end"):      # (not the first s_endpgm: an early return has one of its own)
-                cur = None
-            else:
-                kernels[cur].append(line.split(";")[0])
+    kernels, _, text = kernel_asm("sgc_kernels.hip")
     meta = {}
     for block in text.split("- .agpr_count:")[1:] if "- .agpr_count:" in text else []:
         name = re.search(r"\.name:\s+(\S+)", block)

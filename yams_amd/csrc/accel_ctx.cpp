@@ -167,6 +167,21 @@ yams_status_t pinned_get(yams_accel_ctx* ctx, size_t bytes, void** out) {
     return YAMS_OK;
 }
 
+yams_status_t flags_get(yams_accel_ctx* ctx, uint32_t words, uint32_t** d_flags) {
+    YA_TRY(ws_get(ctx, "flags", 64, (void**)d_flags));
+    YA_HIP(ctx, hipMemsetAsync(*d_flags, 0, static_cast<size_t>(words) * 4, ctx->stream));
+    return YAMS_OK;
+}
+
+yams_status_t read_words(yams_accel_ctx* ctx, const void* d_src, uint32_t words, void* out) {
+    void* h;
+    YA_TRY(pinned_get(ctx, 64, &h));
+    YA_HIP(ctx, hipMemcpyAsync(h, d_src, static_cast<size_t>(words) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(out, h, static_cast<size_t>(words) * 4);
+    return YAMS_OK;
+}
+
 static hipEvent_t get_event(yams_accel_ctx* ctx) {
     if (!ctx->event_pool.empty()) {
         hipEvent_t e = ctx->event_pool.back();

@@ -82,6 +82,15 @@ yams_status_t ws_get(yams_accel_ctx* ctx, const char* name, size_t bytes, void**
 // the bytes given back.  For calls whose buffers scale with the CALL (GiB-sized ingest batches), not with the device.
 size_t ws_trim(yams_accel_ctx* ctx, size_t keep_bytes);
 yams_status_t pinned_get(yams_accel_ctx* ctx, size_t bytes, void** out);
+// The refusal read-back of the entries whose checks need the arrays.  flags_get: a device block of `words` uint32 (at most 16),
+// zeroed on the context's stream, for check kernels to OR their refusals into.  One workspace serves every family: a block is
+// finished with before the entry that took it returns or calls another entry.
+yams_status_t flags_get(yams_accel_ctx* ctx, uint32_t words, uint32_t** d_flags);
+// read_words: copies `words` uint32 (at most 16) at a device address to `out` (any host memory, a local as a rule: a flag word,
+// the uint64_t off[lists] of a device offsets array as two words, a small block of counters) behind what the stream holds, and
+// SYNCHRONISES the stream.  The value travels through the pinned buffer but no pointer into it leaves the call, so a later
+// pinned_get may grow it.
+yams_status_t read_words(yams_accel_ctx* ctx, const void* d_src, uint32_t words, void* out);
 
 // Host -> device copy of `bytes` at `src` (any host memory) to `dst` on `stream`, ordered on the stream like
 // hipMemcpyAsync (the caller synchronises the stream before it reads `dst` from another one).  Large pageable sources:

@@ -7,33 +7,11 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "arg_checks.h"
+#include "artifact_launch.h"
+#include "kmeans_launch.h"
 
 using namespace yams_accel;
-
-namespace yams_accel {
-// kmeans_kernels.hip
-hipError_t launch_kmeans_norm(hipStream_t st, const float* x, uint64_t n, uint32_t dim, double2* norms, uint32_t* nonfinite);
-// artifact_kernels.hip
-hipError_t launch_artifact_check(hipStream_t st, const uint64_t* off, uint64_t lists, uint64_t total, const uint32_t* idx, uint32_t limit,
-                                 uint32_t* flags);
-hipError_t launch_artifact_check_primary(hipStream_t st, const uint32_t* primary, uint64_t n, uint32_t c, uint32_t* flags);
-hipError_t launch_artifact_owner(hipStream_t st, const uint64_t* off, uint32_t lists, uint64_t total, uint32_t* owner);
-hipError_t launch_artifact_centroids(hipStream_t st, const float* x, uint32_t dim, const uint64_t* off, const uint32_t* members, uint32_t c,
-                                     float* out, uint32_t* out_counts);
-hipError_t launch_artifact_rep_init(hipStream_t st, const uint64_t* off, uint32_t c, const uint8_t* centroid_empty, uint32_t n_extra,
-                                    uint32_t* limit, uint32_t* last);
-hipError_t launch_artifact_rep_pass(hipStream_t st, const float* x, uint32_t dim, const double2* row_norm, const uint64_t* off,
-                                    const uint32_t* cand, const uint32_t* owner, uint64_t total, uint32_t c, const float* cents,
-                                    const double2* cent_norm, const uint32_t* limit, uint32_t* last, uint32_t s, uint32_t n_extra,
-                                    uint8_t* used, double* min_dist, uint32_t* out_selected);
-hipError_t launch_artifact_residual_dense(hipStream_t st, const float* x, uint64_t n, uint32_t dim, const float* cents, uint32_t c,
-                                          const uint32_t* primary, bool fused, double* out_norm, double* out_dot);
-hipError_t launch_artifact_residual_list(hipStream_t st, const float* x, uint32_t dim, const float* cents, const uint32_t* primary,
-                                         const uint32_t* doc_of, const uint32_t* cand, uint64_t total, bool fused, double* out_norm,
-                                         double* out_dot);
-hipError_t launch_artifact_primary_norm(hipStream_t st, const float* x, uint64_t n, uint32_t dim, const float* cents, const uint32_t* primary,
-                                        bool fused, double* out_norm);
-}
 
 namespace {
 
@@ -51,38 +29,23 @@ yams_status_t check_shape(yams_accel_ctx* ctx, const float* rows, uint64_t n, ui
     return YAMS_OK;
 }
 
-// off[lists] of a device offsets array.  Synchronises.
-yams_status_t read_total(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t lists, uint64_t* total) {
-    uint64_t* h;
-    YA_TRY(pinned_get(ctx, 64, (void**)&h));
-    YA_HIP(ctx, hipMemcpyAsync(h, d_off + lists, 8, hipMemcpyDeviceToHost, ctx->stream));
-    YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *total = *h;
-    return YAMS_OK;
-}
-
 // The list checks: offsets from 0, never decreasing, entries < limit.  Synchronises.
 yams_status_t check_lists(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t lists, uint64_t total, const uint32_t* d_idx, uint32_t limit,
                           const uint32_t* d_primary, uint64_t n, uint32_t c, const char* what) {
     hipStream_t st = ctx->stream;
-    uint32_t* d_flags; uint32_t* h_flags;
-    YA_TRY(ws_get(ctx, "art_flags", 16, (void**)&d_flags));
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_flags));
-    YA_HIP(ctx, hipMemsetAsync(d_flags, 0, 16, st));
+    uint32_t* d_flags; uint32_t flags;
+    YA_TRY(flags_get(ctx, 4, &d_flags));
     if (d_off) YA_HIP(ctx, launch_artifact_check(st, d_off, lists, total, d_idx, limit, d_flags));
     if (d_primary) YA_HIP(ctx, launch_artifact_check_primary(st, d_primary, n, c, d_flags));
-    YA_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    if (*h_flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": the offsets do not start at 0 or decrease");
-    if (*h_flags & 2u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": an index is out of range");
+    YA_TRY(read_words(ctx, d_flags, 1, &flags));
+    if (flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": the offsets do not start at 0 or decrease");
+    if (flags & 2u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": an index is out of range");
     return YAMS_OK;
 }
 
 // what the _host twins judge before they size an upload by the offsets
 yams_status_t host_offsets(yams_accel_ctx* ctx, const uint64_t* off, uint64_t lists, uint64_t* total) {
-    if (off[0] != 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
-    for (uint64_t i = 0; i < lists; ++i)
-        if (off[i + 1] < off[i]) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+    if (!offsets_ascend(off, lists)) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
     *total = off[lists];
     if (*total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
     return YAMS_OK;
@@ -101,7 +64,7 @@ extern "C" yams_status_t yams_cluster_centroids_device(yams_accel_ctx* ctx, cons
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     uint64_t total;
-    YA_TRY(read_total(ctx, cluster_offsets, n_clusters, &total));
+    YA_TRY(read_words(ctx, cluster_offsets + n_clusters, 2, &total));
     if (total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
     if (total && !members) return fail(ctx, YAMS_ERR_INVALID_ARG, "null members");
     YA_TRY(check_lists(ctx, cluster_offsets, n_clusters, total, members, static_cast<uint32_t>(n), nullptr, 0, 0, "members"));
@@ -157,23 +120,20 @@ extern "C" yams_status_t yams_cluster_representatives_device(yams_accel_ctx* ctx
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     uint64_t total;
-    YA_TRY(read_total(ctx, cluster_offsets, n_clusters, &total));
+    YA_TRY(read_words(ctx, cluster_offsets + n_clusters, 2, &total));
     if (total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
     if (total && !candidates) return fail(ctx, YAMS_ERR_INVALID_ARG, "null candidates");
     YA_TRY(check_lists(ctx, cluster_offsets, n_clusters, total, candidates, static_cast<uint32_t>(n), nullptr, 0, 0, "candidates"));
 
     // (lhsNorm, sqrt) of every row and of every centroid, once: the same chain whoever asks.  A non-finite row refuses the call.
-    double2* d_na; double2* d_nb; uint32_t* d_flag; uint32_t* h_flag;
+    double2* d_na; double2* d_nb; uint32_t* d_flag; uint32_t nonfinite;
     YA_TRY(ws_get(ctx, "art_row_norm", static_cast<size_t>(n ? n : 1) * sizeof(double2), (void**)&d_na));
     YA_TRY(ws_get(ctx, "art_cent_norm", static_cast<size_t>(n_clusters) * sizeof(double2), (void**)&d_nb));
-    YA_TRY(ws_get(ctx, "art_flags", 16, (void**)&d_flag));
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_flag));
-    YA_HIP(ctx, hipMemsetAsync(d_flag, 0, 16, st));
+    YA_TRY(flags_get(ctx, 4, &d_flag));
     YA_HIP(ctx, launch_kmeans_norm(st, rows, n, dim, d_na, d_flag));
     YA_HIP(ctx, launch_kmeans_norm(st, centroids, n_clusters, dim, d_nb, nullptr));
-    YA_HIP(ctx, hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    if (*h_flag) return fail(ctx, YAMS_ERR_INVALID_ARG, "a row holds a non-finite value");
+    YA_TRY(read_words(ctx, d_flag, 1, &nonfinite));
+    if (nonfinite) return fail(ctx, YAMS_ERR_INVALID_ARG, "a row holds a non-finite value");
 
     uint32_t* d_owner; uint32_t* d_limit; uint32_t* d_last; uint8_t* d_used; double* d_min;
     const size_t t1 = static_cast<size_t>(total ? total : 1);
@@ -270,7 +230,7 @@ extern "C" yams_status_t yams_cluster_residuals_device(yams_accel_ctx* ctx, cons
     const bool fused = form == YAMS_RESIDUAL_FUSED;
     uint64_t total = 0;
     if (cand_offsets) {
-        YA_TRY(read_total(ctx, cand_offsets, n, &total));
+        YA_TRY(read_words(ctx, cand_offsets + n, 2, &total));
         if (total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
     }
     if (cand_offsets || primary)

@@ -32,7 +32,9 @@
 #include <cfloat>
 
 #include "common.h"
+#include "artifact_launch.h"
 #include "cosine_tail.h"
+#include "form_step.h"
 #include "row_walk.h"
 
 namespace yams_accel {
@@ -54,11 +56,6 @@ __device__ __forceinline__ void ar_stage_gather(const float* __restrict__ base, 
         const uint32_t row = idx[r];
         tile[r][dc] = (row != kArNone && d0 + dc < dim) ? base[static_cast<uint64_t>(row) * dim + d0 + dc] : 0.0f;
     }
-}
-
-template <bool FUSED>
-__device__ __forceinline__ double ar_mul_add(double a, double b, double acc) {
-    return FUSED ? __fma_rn(a, b, acc) : __dadd_rn(acc, __dmul_rn(a, b));
 }
 
 } // namespace
@@ -275,8 +272,8 @@ __global__ __launch_bounds__(kArThreads) void artifact_residual_dense_kernel(con
 #pragma unroll
                 for (int j = 0; j < kRsBlock; ++j) {
                     const double r = __dsub_rn(a[i], b[j]);
-                    an[i][j] = ar_mul_add<FUSED>(r, r, an[i][j]);
-                    ad[i][j] = ar_mul_add<FUSED>(q[i], r, ad[i][j]);
+                    an[i][j] = form_mul_add<FUSED>(r, r, an[i][j]);
+                    ad[i][j] = form_mul_add<FUSED>(q[i], r, ad[i][j]);
                 }
         }
     }
@@ -326,10 +323,10 @@ __global__ __launch_bounds__(kArThreads) void artifact_residual_pairs_kernel(con
             const double q = has ? __dsub_rn(ev, static_cast<double>(tp[t][e])) : 0.0;
             if (CAND) {
                 const double r = __dsub_rn(ev, static_cast<double>(tc[t][e]));
-                nrm = ar_mul_add<FUSED>(r, r, nrm);
-                dot = ar_mul_add<FUSED>(q, r, dot);
+                nrm = form_mul_add<FUSED>(r, r, nrm);
+                dot = form_mul_add<FUSED>(q, r, dot);
             } else {
-                nrm = ar_mul_add<FUSED>(q, q, nrm);
+                nrm = form_mul_add<FUSED>(q, q, nrm);
             }
         }
     }
@@ -341,7 +338,6 @@ __global__ __launch_bounds__(kArThreads) void artifact_residual_pairs_kernel(con
 // ---- launchers ------------------------------------------------------------------------------------------------------------
 static inline uint32_t ar_blocks(uint64_t n, uint32_t per) { return static_cast<uint32_t>((n + per - 1) / per); }
 
-// flags: 1 = the offsets do not start at 0, decrease or pass `total`; 2 = an index is out of range
 hipError_t launch_artifact_check(hipStream_t st, const uint64_t* off, uint64_t lists, uint64_t total, const uint32_t* idx, uint32_t limit,
                                  uint32_t* flags) {
     if (lists) artifact_check_offsets_kernel<<<ar_blocks(lists, kArThreads), kArThreads, 0, st>>>(off, lists, total, flags);
@@ -371,7 +367,6 @@ hipError_t launch_artifact_rep_init(hipStream_t st, const uint64_t* off, uint32_
     return hipGetLastError();
 }
 
-// one pass of the selection: the distances of every unused candidate, then every cluster's winner
 hipError_t launch_artifact_rep_pass(hipStream_t st, const float* x, uint32_t dim, const double2* row_norm, const uint64_t* off,
                                     const uint32_t* cand, const uint32_t* owner, uint64_t total, uint32_t c, const float* cents,
                                     const double2* cent_norm, const uint32_t* limit, uint32_t* last, uint32_t s, uint32_t n_extra,

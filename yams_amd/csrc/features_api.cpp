@@ -6,15 +6,11 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "arg_checks.h"
+#include "artifact_launch.h"
 #include "features_launch.h"
 
 using namespace yams_accel;
-
-namespace yams_accel {
-// artifact_kernels.hip: flags |= 1 for offsets that do not start at 0, decrease or pass `total`; |= 2 for an index >= limit
-hipError_t launch_artifact_check(hipStream_t st, const uint64_t* off, uint64_t lists, uint64_t total, const uint32_t* idx, uint32_t limit,
-                                 uint32_t* flags);
-}
 
 namespace {
 
@@ -22,25 +18,16 @@ static_assert(YAMS_FEATURES_MAX_DIM == kFeatMaxDim && YAMS_FEATURES_MAX_SIG_LEN 
 constexpr uint64_t kMaxRows = 1ull << 31;
 constexpr uint64_t kMaxEntries = 1ull << 32;
 
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    if (!a || !b || !a_bytes || !b_bytes) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 // The list checks on the device: offsets from 0, never decreasing, ending at `total`; entries < limit.  Synchronises.
 yams_status_t check_lists(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t lists, uint64_t total, const uint32_t* d_idx, uint32_t limit,
                           const char* what) {
     hipStream_t st = ctx->stream;
-    uint32_t* d_flags; uint32_t* h_flags;
-    YA_TRY(ws_get(ctx, "feat_flags", 16, (void**)&d_flags));
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_flags));
-    YA_HIP(ctx, hipMemsetAsync(d_flags, 0, 16, st));
+    uint32_t* d_flags; uint32_t flags;
+    YA_TRY(flags_get(ctx, 4, &d_flags));
     YA_HIP(ctx, launch_artifact_check(st, d_off, d_off ? lists : 0, total, d_idx, limit, d_flags));
-    YA_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    if (*h_flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": the offsets do not start at 0 or decrease");
-    if (*h_flags & 2u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": an index is out of range");
+    YA_TRY(read_words(ctx, d_flags, 1, &flags));
+    if (flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": the offsets do not start at 0 or decrease");
+    if (flags & 2u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": an index is out of range");
     return YAMS_OK;
 }
 
@@ -127,11 +114,8 @@ extern "C" yams_status_t yams_features_aggregate_device(yams_accel_ctx* ctx, con
     if (n_docs == 0) return YAMS_OK;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    uint64_t* h_total;
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_total));
-    YA_HIP(ctx, hipMemcpyAsync(h_total, doc_offsets + n_docs, 8, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    const uint64_t total = *h_total;
+    uint64_t total;
+    YA_TRY(read_words(ctx, doc_offsets + n_docs, 2, &total));
     YA_TRY(check_aggregate_total(ctx, rows, n_records, dim, records, total, n_docs, out, out_counts));
     YA_TRY(check_lists(ctx, doc_offsets, n_docs, total, records, static_cast<uint32_t>(n_records), "records"));
     {
@@ -150,9 +134,7 @@ extern "C" yams_status_t yams_features_aggregate_host(yams_accel_ctx* ctx, const
     YA_TRY(check_aggregate(ctx, n_records, dim, doc_offsets, n_docs, out, out_counts));
     if (n_docs == 0) return YAMS_OK;
     // judged here, before an upload is sized by them
-    if (doc_offsets[0] != 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "records: the offsets do not start at 0 or decrease");
-    for (uint64_t i = 0; i < n_docs; ++i)
-        if (doc_offsets[i + 1] < doc_offsets[i]) return fail(ctx, YAMS_ERR_INVALID_ARG, "records: the offsets do not start at 0 or decrease");
+    if (!offsets_ascend(doc_offsets, n_docs)) return fail(ctx, YAMS_ERR_INVALID_ARG, "records: the offsets do not start at 0 or decrease");
     const uint64_t total = doc_offsets[n_docs];
     YA_TRY(check_aggregate_total(ctx, rows, n_records, dim, records, total, n_docs, out, out_counts));
     (void)hipSetDevice(ctx->device);

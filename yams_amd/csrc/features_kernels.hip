@@ -30,6 +30,7 @@
 // square root); the device code keeps f32 denormals.  The squares of floats are exact in fp64: fma(v, v, acc) == acc + v * v.
 #include "common.h"
 #include "features_launch.h"
+#include "form_step.h"
 #include "row_chains.h"
 
 namespace yams_accel {
@@ -57,11 +58,6 @@ __device__ __forceinline__ FeatRowParts feat_row_parts(const FeatComposeArgs& a,
     const float t = __fsub_rn(__fsub_rn(1.0f, p.a_e), p.a_m);
     p.a_d = (0.0f < t) ? t : 0.0f;      // std::max(0.0F, t) = (0.0F < t) ? t : 0.0F: a NaN gives 0.0F
     return p;
-}
-
-template <bool FUSED>
-__device__ __forceinline__ double feat_mul_add(double a, double b, double acc) {
-    return FUSED ? __fma_rn(a, b, acc) : __dadd_rn(acc, __dmul_rn(a, b));
 }
 
 } // namespace
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(kFeatVarLanes) void features_variance_kernel(const 
         for (int j = 0; j < kFeatVarRows; ++j)
             if (i0 + j < m) {
                 const double r = __dsub_rn(static_cast<double>(cur[j]), mean);
-                var = feat_mul_add<FUSED>(r, r, var);
+                var = form_mul_add<FUSED>(r, r, var);
             }
 #pragma unroll
         for (int j = 0; j < kFeatVarRows; ++j) cur[j] = nxt[j];

@@ -1,7 +1,8 @@
-// fp64_tile.h — the exact fp64 tile of kmeans_assign_kernel and semgraph_pairs_kernel: 128 A rows x 64 B rows of float
-// vectors, one fp64 dot product per pair.  Device code for the .hip files, plus the launchers' predicate for the VEC form.
+// fp64_tile.h — the fp64 tile of kmeans_assign_kernel, semgraph_pairs_kernel, route_score_tile_kernel and persist_pairs_kernel:
+// 128 A rows x 64 B rows of float vectors, one fp64 chain per pair (a dot product unless the caller brings its own step).
+// Device code for the .hip files, plus the launchers' predicate for the VEC form.
 //
-// Exactness (the bit-for-bit claim of both features lives here): the product of two floats is exact in fp64, so
+// Exactness of the default step (the bit-for-bit claim of the dot-product callers lives here): the product of two floats is exact in fp64, so
 // fma(a, b, acc) == acc + a * b bit for bit; every pair's chain walks the dimension in element order in ONE lane and is never
 // split, so it is the reference's scalar loop.  A chunk that reaches past `dim` (and a row that is not live) is filled with
 // +0.0f: a chain that starts at +0.0 can never hold -0.0 (x + y is -0.0 only when both are), so adding the exact product +0.0
@@ -33,10 +34,21 @@ inline bool tile_vec_loads(uint32_t dim, const float* a_base, const float* b_bas
     return dim % 4 == 0 && (reinterpret_cast<uintptr_t>(a_base) & 15) == 0 && (reinterpret_cast<uintptr_t>(b_base) & 7) == 0;
 }
 
+// The default step of a chain: the exact-product fma the exactness argument above is about.
+struct TileFmaStep {
+    static __device__ __forceinline__ double step(double a, double b, double acc) { return fma(a, b, acc); }
+};
+
 // acc[i][j] = the chain of A row ty*8 + i and B row tx*4 + j over [0, dim).  a_src / b_src: the rows tile_a_row(t) /
 // tile_b_row(t) (never dereferenced unless a_live / b_live).  Called by the whole workgroup; begins with a barrier (every lane
 // has read the previous call's last chunk) and ends with one.
-template <bool VEC>
+//
+// The accumulate step is a parameter: acc = Step::step(a, b, acc), once per element in element order.  The staging (zero fill
+// past `dim`, one barrier per chunk, double buffering) and the one-lane-per-chain order are the same for every step.  The
+// exactness argument at the top of this header covers the default step only.  A caller whose step has an inexact product owns
+// its own argument — what its step makes of the +0.0 fill, which host form its bits follow — as persistence_kernels.hip does
+// for d = a - b, acc (+)= d * d.
+template <bool VEC, class Step = TileFmaStep>
 __device__ __forceinline__ void tile_chains(TileLdsA& sa, TileLdsB& sb, const float* __restrict__ a_src, bool a_live,
                                             const float* __restrict__ b_src, bool b_live, uint32_t dim,
                                             double (&acc)[kTileRB][kTileCB]) {
@@ -92,7 +104,7 @@ __device__ __forceinline__ void tile_chains(TileLdsA& sa, TileLdsB& sb, const fl
 #pragma unroll
             for (int i = 0; i < kTileRB; ++i)
 #pragma unroll
-                for (int j = 0; j < kTileCB; ++j) acc[i][j] = fma(a[i], b[j], acc[i][j]);
+                for (int j = 0; j < kTileCB; ++j) acc[i][j] = Step::step(a[i], b[j], acc[i][j]);
         }
         if (more) store(buf ^ 1);
         __syncthreads();

@@ -11,26 +11,9 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "kmeans_launch.h"
 
 using namespace yams_accel;
-
-namespace yams_accel { // kmeans_kernels.hip
-hipError_t launch_kmeans_norm(hipStream_t st, const float* x, uint64_t n, uint32_t dim, double2* norms, uint32_t* nonfinite);
-hipError_t launch_kmeans_init_dist(hipStream_t st, const float* x, uint64_t n, uint32_t dim, const double2* row_norm, const float* cents,
-                                   const double2* cent_norm, uint32_t centroid, const uint8_t* selected, double* min_dist,
-                                   double* part_val, uint32_t* part_idx);
-hipError_t launch_kmeans_own_dist(hipStream_t st, const float* x, uint64_t n, uint32_t dim, const double2* row_norm, const float* cents,
-                                  const double2* cent_norm, const uint32_t* membership, double* out_dist);
-hipError_t launch_kmeans_pick(hipStream_t st, const double* part_val, const uint32_t* part_idx, uint32_t n_parts, uint32_t explicit_index,
-                              const float* x, uint32_t dim, uint8_t* selected, float* cents, double2* cent_norm, uint32_t slot);
-hipError_t launch_kmeans_assign(hipStream_t st, const float* x, uint64_t n, uint32_t dim, const double2* row_norm, const float* cents,
-                                const double2* cent_norm, uint32_t k, const uint8_t* skip, uint32_t* membership, uint32_t* changed,
-                                uint32_t* out_assign, double* out_dist);
-hipError_t launch_kmeans_group(hipStream_t st, const uint32_t* membership, uint64_t n, uint32_t k, uint32_t* counts, uint32_t* offsets,
-                               uint32_t* members);
-hipError_t launch_kmeans_centroids(hipStream_t st, const float* x, uint32_t dim, const uint32_t* members, const uint32_t* offsets,
-                                   const uint32_t* counts, uint32_t k, int only, float* cents, double2* cent_norm);
-}
 
 namespace {
 
@@ -57,15 +40,12 @@ uint64_t effective_k(uint64_t n, uint32_t k) {
 // (na, sqrt(na)) of every row; a non-finite row refuses the call.  Synchronises.
 yams_status_t row_norms(yams_accel_ctx* ctx, const float* rows, uint64_t n, uint32_t dim, double2** out) {
     hipStream_t st = ctx->stream;
-    double2* d_na; uint32_t* d_flag; uint32_t* h_flag;
+    double2* d_na; uint32_t* d_flag; uint32_t nonfinite;
     YA_TRY(ws_get(ctx, "km_row_norm", static_cast<size_t>(n) * sizeof(double2), (void**)&d_na));
-    YA_TRY(ws_get(ctx, "km_flag", 16, (void**)&d_flag));
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_flag));
-    YA_HIP(ctx, hipMemsetAsync(d_flag, 0, 16, st));
+    YA_TRY(flags_get(ctx, 4, &d_flag));
     YA_HIP(ctx, launch_kmeans_norm(st, rows, n, dim, d_na, d_flag));
-    YA_HIP(ctx, hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    if (*h_flag) return fail(ctx, YAMS_ERR_INVALID_ARG, "a row holds a non-finite value");
+    YA_TRY(read_words(ctx, d_flag, 1, &nonfinite));
+    if (nonfinite) return fail(ctx, YAMS_ERR_INVALID_ARG, "a row holds a non-finite value");
     *out = d_na;
     return YAMS_OK;
 }

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "cosine_tail.h"
 #include "fp64_tile.h"
+#include "kmeans_launch.h"
 #include "row_walk.h"
 
 namespace yams_accel {
@@ -377,7 +378,6 @@ hipError_t launch_kmeans_assign(hipStream_t st, const float* x, uint64_t n, uint
     return hipGetLastError();
 }
 
-// counts / offsets / members of the current membership (counts must be zero on entry)
 hipError_t launch_kmeans_group(hipStream_t st, const uint32_t* membership, uint64_t n, uint32_t k, uint32_t* counts, uint32_t* offsets,
                                uint32_t* members) {
     kmeans_hist_kernel<<<km_blocks(n, kKmThreads), kKmThreads, 0, st>>>(membership, n, counts);

@@ -50,22 +50,20 @@ yams_status_t run(yams_accel_ctx* ctx, const float* d_rows, uint64_t n, uint32_t
     h_weights.clear();
     if (d_dist_used) *d_dist_used = nullptr;
     if (m == 0) return YAMS_OK;
-    uint32_t* d_flags; uint32_t* h_flags;
-    YA_TRY(ws_get(ctx, "persist_flags", 16, (void**)&d_flags));
-    YA_TRY(pinned_get(ctx, 64 + static_cast<size_t>(m) * 8, (void**)&h_flags));
-    YA_HIP(ctx, hipMemsetAsync(d_flags, 0, 16, st));
+    uint32_t* d_flags; uint32_t flags;
+    YA_TRY(flags_get(ctx, 4, &d_flags));
     YA_HIP(ctx, launch_persist_check(st, d_rows, n, dim, d_select, m, d_flags));
-    YA_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    if (*h_flags & kPersistFlagRange) return fail(ctx, YAMS_ERR_INVALID_ARG, "a select entry is out of range");
-    if (*h_flags & kPersistFlagNonFinite) return fail(ctx, YAMS_ERR_INVALID_ARG, "a selected row holds a non-finite value");
+    YA_TRY(read_words(ctx, d_flags, 1, &flags));
+    if (flags & kPersistFlagRange) return fail(ctx, YAMS_ERR_INVALID_ARG, "a select entry is out of range");
+    if (flags & kPersistFlagNonFinite) return fail(ctx, YAMS_ERR_INVALID_ARG, "a selected row holds a non-finite value");
 
-    double* d_mat = d_dist; uint32_t* d_hist; uint64_t* d_state; double* d_w; void* d_tree;
+    double* d_mat = d_dist; uint32_t* d_hist; uint64_t* d_state; double* d_w; void* d_tree; uint64_t* h_pin;
     if (!d_mat) YA_TRY(ws_get(ctx, "persist_matrix", static_cast<size_t>(m) * m * 8, (void**)&d_mat));
     YA_TRY(ws_get(ctx, "persist_hist", kPersistSelectPasses * 256 * 4, (void**)&d_hist));
     YA_TRY(ws_get(ctx, "persist_state", kPersistSelectStateWords * 8, (void**)&d_state));
     YA_TRY(ws_get(ctx, "persist_weights", static_cast<size_t>(m) * 8, (void**)&d_w));
     YA_TRY(ws_get(ctx, "persist_tree", persist_tree_scratch_bytes(m), &d_tree));
+    YA_TRY(pinned_get(ctx, 64 + static_cast<size_t>(m) * 8, (void**)&h_pin));      // [0]: the percentile's pattern, [8 ..]: the weights
     if (d_dist_used) *d_dist_used = d_mat;
 
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -74,7 +72,6 @@ yams_status_t run(yams_accel_ctx* ctx, const float* d_rows, uint64_t n, uint32_t
         for (auto& e : ev)
             if (hipEventCreate(&e) != hipSuccess) { drop_events(); return hip_fail(ctx, hipGetLastError(), "hipEventCreate"); }
     auto mark = [&](int i) { return out_stage_ms ? hipEventRecord(ev[i], st) : hipSuccess; };
-    auto* h_pin = reinterpret_cast<uint64_t*>(h_flags);      // [0]: the percentile's pattern, [8 ..]: the weights
     auto work = [&]() -> hipError_t {
         hipError_t e = mark(0);
         if (e == hipSuccess) e = launch_persist_pairs(st, d_rows, dim, d_select, m, form == YAMS_RESIDUAL_FUSED, d_mat);

@@ -9,13 +9,12 @@
 //
 // Launches per call:
 //   persist_check_kernel        a select entry >= n, a non-finite element of a selected row: found before anything is written
-//   persist_pairs_kernel        THE HOT PATH: the 128 x 64 tile shape of fp64_tile.h (its constants, LDS types and staging
-//                               roles are used as they are), 8 x 4 chains per lane, each chain in ONE lane in element order.
-//                               The step is not fp64_tile.h's: d = a - b, then acc (+)= d * d, and d * d is NOT exact in fp64
-//                               (d carries up to 53 bits), so the bits depend on whether the host contracted the step into an
-//                               fma.  FUSED = one fma; otherwise __dmul_rn then __dadd_rn, which the compiler may not contract.
-//                               fp64_tile.h stays as it is: its staging lives inside tile_chains next to the fma, so
-//                               pair_chains below is a sibling core that repeats the staging rather than a shared one.
+//   persist_pairs_kernel        THE HOT PATH: tile_chains of fp64_tile.h (the 128 x 64 tile, its staging and its 8 x 4 chains
+//                               per lane, each chain in ONE lane in element order) with this file's step, PairStep, in place of
+//                               the default fma: d = a - b, then acc (+)= d * d.  d * d is NOT exact in fp64 (d carries up to 53
+//                               bits), so fp64_tile.h's exactness argument does not cover it and the bits depend on whether the
+//                               host contracted the step into an fma: form_mul_add (form_step.h) has both forms.  What is argued
+//                               here instead: a - b is one correctly rounded subtraction in either form;
 //                               (-d)^2 == d^2 bit for bit, so the matrix is symmetric: only tiles that touch the upper triangle
 //                               are computed (about half the work at large m), every value is stored at (i, j) and, eight
 //                               consecutive doubles per lane, at (j, i).  Each (i < j) lies in exactly one computed tile, so no
@@ -32,6 +31,7 @@
 //                               threshold the number of tree edges at or below it is m minus the components of the graph of
 //                               such edges).
 #include "common.h"
+#include "form_step.h"
 #include "fp64_tile.h"
 #include "persistence_launch.h"
 
@@ -53,73 +53,13 @@ __global__ __launch_bounds__(256) void persist_check_kernel(const float* __restr
     if (bad) atomicOr(flags, kPersistFlagNonFinite);
 }
 
-// acc[i][j] = the chain of (A row ty*8 + i) - (B row tx*4 + j) over [0, dim): the staging of tile_chains (fp64_tile.h), the
-// step of pairwiseDistance.  Called by the whole workgroup.
-template <bool VEC, bool FUSED>
-__device__ __forceinline__ void pair_chains(TileLdsA& sa, TileLdsB& sb, const float* __restrict__ a_src, bool a_live,
-                                            const float* __restrict__ b_src, bool b_live, uint32_t dim,
-                                            double (&acc)[kTileRB][kTileCB]) {
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const int ar = tile_a_row(t), ad = (t & 1) * 4, br = tile_b_row(t), bd = (t & 3) * 2;
-    const uint32_t n_chunks = (dim + kTileChunk - 1) / kTileChunk;
-    float fa[4], fb[2];
-    auto load = [&](uint32_t d0) {
-        if (VEC) {
-            const float4 v = (a_live && d0 + ad < dim) ? *reinterpret_cast<const float4*>(a_src + d0 + ad) : make_float4(0.f, 0.f, 0.f, 0.f);
-            fa[0] = v.x; fa[1] = v.y; fa[2] = v.z; fa[3] = v.w;
-            const float2 w = (b_live && d0 + bd < dim) ? *reinterpret_cast<const float2*>(b_src + d0 + bd) : make_float2(0.f, 0.f);
-            fb[0] = w.x; fb[1] = w.y;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) fa[e] = (a_live && d0 + ad + e < dim) ? a_src[d0 + ad + e] : 0.0f;
-#pragma unroll
-            for (int e = 0; e < 2; ++e) fb[e] = (b_live && d0 + bd + e < dim) ? b_src[d0 + bd + e] : 0.0f;
-        }
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sa[buf][ad + e][ar] = static_cast<double>(fa[e]);
-#pragma unroll
-        for (int e = 0; e < 2; ++e) sb[buf][bd + e][br] = static_cast<double>(fb[e]);
-    };
-#pragma unroll
-    for (int i = 0; i < kTileRB; ++i)
-#pragma unroll
-        for (int j = 0; j < kTileCB; ++j) acc[i][j] = 0.0;
-
-    __syncthreads();
-    load(0);
-    store(0);
-    __syncthreads();
-    for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-        const int buf = ch & 1;
-        const bool more = ch + 1 < n_chunks;
-        if (more) load((ch + 1) * kTileChunk);
-#pragma unroll 2
-        for (int e = 0; e < kTileChunk; ++e) {
-            double a[kTileRB], b[kTileCB];
-#pragma unroll
-            for (int i = 0; i < kTileRB; i += 2) {
-                const double2 v = *reinterpret_cast<const double2*>(&sa[buf][e][ty * kTileRB + i]);
-                a[i] = v.x; a[i + 1] = v.y;
-            }
-#pragma unroll
-            for (int j = 0; j < kTileCB; j += 2) {
-                const double2 v = *reinterpret_cast<const double2*>(&sb[buf][e][tx * kTileCB + j]);
-                b[j] = v.x; b[j + 1] = v.y;
-            }
-#pragma unroll
-            for (int i = 0; i < kTileRB; ++i)
-#pragma unroll
-                for (int j = 0; j < kTileCB; ++j) {
-                    const double d = __dsub_rn(a[i], b[j]);
-                    acc[i][j] = FUSED ? __fma_rn(d, d, acc[i][j]) : __dadd_rn(acc[i][j], __dmul_rn(d, d));
-                }
-        }
-        if (more) store(buf ^ 1);
-        __syncthreads();
+// The step of pairwiseDistance for tile_chains (fp64_tile.h): d = a - b, then acc (+)= d * d in the host's form.
+template <bool FUSED> struct PairStep {
+    static __device__ __forceinline__ double step(double a, double b, double acc) {
+        const double d = __dsub_rn(a, b);
+        return form_mul_add<FUSED>(d, d, acc);
     }
-}
+};
 
 // Grid: x = one workgroup per 128 points (the rows i of the tile), y = one per 64 points (the columns j).  A tile wholly below
 // the diagonal leaves at once (before any barrier).
@@ -136,7 +76,7 @@ __global__ __launch_bounds__(kTileThreads, 2) void persist_pairs_kernel(const fl
     const bool a_live = a_pt < m, b_live = b_pt < m;
     const uint64_t a_row = a_live ? (select ? select[a_pt] : a_pt) : 0u, b_row = b_live ? (select ? select[b_pt] : b_pt) : 0u;
     double acc[kTileRB][kTileCB];
-    pair_chains<VEC, FUSED>(sa, sb, rows + a_row * dim, a_live, rows + b_row * dim, b_live, dim, acc);
+    tile_chains<VEC, PairStep<FUSED>>(sa, sb, rows + a_row * dim, a_live, rows + b_row * dim, b_live, dim, acc);
 #pragma unroll
     for (int i = 0; i < kTileRB; ++i) {
         const uint32_t r = row0 + ty * kTileRB + i;

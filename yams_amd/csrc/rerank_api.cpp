@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "accel_ctx.h"
+#include "arg_checks.h"
 #include "rerank_launch.h"
 
 using namespace yams_accel;
@@ -17,12 +18,6 @@ static_assert(YAMS_RERANK_MAX_DIM == kRerankMaxDim && YAMS_RERANK_MAX_DOC_TOKENS
                   YAMS_RERANK_MAX_DOCS == kRerankMaxDocs && YAMS_RERANK_MAX_ROWMAX == kRerankMaxRowMax,
               "the header's limits are the launchers'");
 static_assert(YAMS_RERANK_PATH_VALU == kRerankValu && YAMS_RERANK_PATH_MFMA == kRerankMfma, "the diag's path is the launcher's");
-
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    if (!a || !b || !a_bytes || !b_bytes) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
 
 RerankPath fused_path() {
 #ifdef YAMS_ACCEL_MEASURE
@@ -72,37 +67,23 @@ yams_status_t check_maxpool_total(yams_accel_ctx* ctx, uint32_t dim, const float
     return YAMS_OK;
 }
 
-// the offsets as the host sees them; the same verdicts as the device check
+// The offsets as the host sees them.  A document too long in front of the first decrease is refused as such (the offsets
+// are judged list by list); every other defect of the offsets is the shared verdict's.
 yams_status_t check_offsets_host(yams_accel_ctx* ctx, const uint64_t* off, uint64_t n_docs) {
-    if (off[0] != 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
-    for (uint64_t i = 0; i < n_docs; ++i) {
-        if (off[i + 1] < off[i]) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+    for (uint64_t i = 0; off[0] == 0 && i < n_docs && off[i + 1] >= off[i]; ++i)
         if (off[i + 1] - off[i] > YAMS_RERANK_MAX_DOC_TOKENS) return fail(ctx, YAMS_ERR_UNSUPPORTED, "a document exceeds YAMS_RERANK_MAX_DOC_TOKENS");
-    }
+    if (!offsets_ascend(off, n_docs)) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
     return YAMS_OK;
 }
 
-// The pool's total (the last offset) and the offsets' checks, over device offsets.  Synchronises.
-yams_status_t device_total(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t n_docs, uint64_t* total) {
-    hipStream_t st = ctx->stream;
-    uint64_t* h_total;
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_total));
-    YA_HIP(ctx, hipMemcpyAsync(h_total, d_off + n_docs, 8, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    *total = *h_total;
-    return YAMS_OK;
-}
+// The offsets' checks over device offsets (total: their last).  Synchronises.
 yams_status_t device_check(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t n_docs, uint64_t total) {
-    hipStream_t st = ctx->stream;
-    uint32_t* d_flags; uint32_t* h_flags;
-    YA_TRY(ws_get(ctx, "rerank_flags", 16, (void**)&d_flags));
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_flags));
-    YA_HIP(ctx, hipMemsetAsync(d_flags, 0, 16, st));
-    YA_HIP(ctx, launch_rerank_check(st, d_off, n_docs, total, YAMS_RERANK_MAX_DOC_TOKENS, d_flags));
-    YA_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    if (*h_flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
-    if (*h_flags & 2u) return fail(ctx, YAMS_ERR_UNSUPPORTED, "a document exceeds YAMS_RERANK_MAX_DOC_TOKENS");
+    uint32_t* d_flags; uint32_t flags;
+    YA_TRY(flags_get(ctx, 4, &d_flags));
+    YA_HIP(ctx, launch_rerank_check(ctx->stream, d_off, n_docs, total, YAMS_RERANK_MAX_DOC_TOKENS, d_flags));
+    YA_TRY(read_words(ctx, d_flags, 1, &flags));
+    if (flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+    if (flags & 2u) return fail(ctx, YAMS_ERR_UNSUPPORTED, "a document exceeds YAMS_RERANK_MAX_DOC_TOKENS");
     return YAMS_OK;
 }
 
@@ -118,7 +99,7 @@ extern "C" yams_status_t yams_rerank_maxsim_device(yams_accel_ctx* ctx, const fl
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     uint64_t total;
-    YA_TRY(device_total(ctx, doc_offsets, n_docs, &total));
+    YA_TRY(read_words(ctx, doc_offsets + n_docs, 2, &total));
     YA_TRY(check_maxsim_total(ctx, query, tq, dim, rows, total, n_docs, out_scores, out_rowmax));
     YA_TRY(device_check(ctx, doc_offsets, n_docs, total));
     const bool fused = form == YAMS_RESIDUAL_FUSED;
@@ -188,7 +169,7 @@ extern "C" yams_status_t yams_rerank_maxpool_device(yams_accel_ctx* ctx, const f
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     uint64_t total;
-    YA_TRY(device_total(ctx, doc_offsets, n_docs, &total));
+    YA_TRY(read_words(ctx, doc_offsets + n_docs, 2, &total));
     YA_TRY(check_maxpool_total(ctx, dim, rows, total, n_docs, out));
     YA_TRY(device_check(ctx, doc_offsets, n_docs, total));
     {

@@ -36,6 +36,7 @@
 // underflows).  Float steps are spelled __fmul_rn / __fadd_rn / __fmaf_rn; the library is built with -ffp-contract=off and keeps
 // f32 denormals.
 #include "common.h"
+#include "form_step.h"
 #include "rerank_launch.h"
 
 namespace yams_accel {
@@ -59,10 +60,6 @@ __device__ __forceinline__ void rerank_take(float& bv, uint32_t& bi, float v, ui
 // token.  kRerankNone (nothing won, the value is the initial -inf) is later than every token.
 __device__ __forceinline__ void rerank_merge(float& bv, uint32_t& bi, float v, uint32_t i) {
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
-
-template <bool FUSED> __device__ __forceinline__ float rerank_step(float a, float b, float sum) {
-    return FUSED ? __fmaf_rn(a, b, sum) : __fadd_rn(sum, __fmul_rn(a, b));
 }
 
 } // namespace
@@ -153,7 +150,7 @@ __global__ __launch_bounds__(kRerankThreads) void rerank_rowmax_kernel(const flo
 #pragma unroll
                     for (int a = 0; a < 4; ++a)
 #pragma unroll
-                        for (int b = 0; b < 8; ++b) acc[a][b] = rerank_step<FUSED>(qa[a], dv[b], acc[a][b]);
+                        for (int b = 0; b < 8; ++b) acc[a][b] = form_mul_add<FUSED>(qa[a], dv[b], acc[a][b]);
                 }
             }
             __syncthreads();

@@ -9,22 +9,9 @@
 #include <cstring>
 
 #include "accel_ctx.h"
+#include "semgraph_launch.h"
 
 using namespace yams_accel;
-
-namespace yams_accel { // semgraph_kernels.hip
-hipError_t launch_semgraph_norm(hipStream_t st, const float* x, uint64_t n, uint32_t dim, float* inv, uint32_t* flags);
-hipError_t launch_semgraph_check(hipStream_t st, uint64_t n, const uint32_t* tie_rank, const uint32_t* source_rows, uint64_t n_sources,
-                                 uint32_t* row_of_rank, uint32_t* flags);
-void semgraph_geometry(uint64_t n, uint64_t n_sources, uint32_t* source_tiles, uint32_t* stripes, uint32_t* tiles_per_stripe);
-hipError_t launch_semgraph_pairs(hipStream_t st, const float* x, uint64_t n, uint32_t dim, const float* inv, const uint32_t* tie_rank,
-                                 const uint32_t* source_rows, uint64_t n_sources, uint32_t K, bool explicit_threshold, float threshold,
-                                 uint32_t source_tiles, uint32_t stripes, uint32_t tiles_per_stripe, uint64_t* part,
-                                 unsigned long long* counts);
-hipError_t launch_semgraph_merge(hipStream_t st, const uint64_t* part, uint32_t stripes, uint32_t K, uint64_t n_sources, const float* x,
-                                 uint32_t dim, const float* inv, const uint32_t* source_rows, const uint32_t* row_of_rank,
-                                 uint32_t* out_rows, float* out_sims, uint32_t* out_counts);
-}
 
 namespace {
 
@@ -68,23 +55,20 @@ extern "C" yams_status_t yams_graph_semantic_neighbors_device(yams_accel_ctx* ct
 
     uint32_t source_tiles, stripes, tiles_per_stripe;
     semgraph_geometry(n, S, &source_tiles, &stripes, &tiles_per_stripe);
-    float* d_inv; uint32_t* d_small; uint32_t* d_ror = nullptr; uint64_t* d_part; uint32_t* h_small;
+    float* d_inv; uint32_t* d_small; uint32_t* d_ror = nullptr; uint64_t* d_part; uint32_t h_small[8];
     YA_TRY(ws_get(ctx, "sg_inv_norm", static_cast<size_t>(n) * 4, (void**)&d_inv));
-    YA_TRY(ws_get(ctx, "sg_small", 32, (void**)&d_small));              // [0] refusal flags, [2..5] the two 64-bit counts
+    YA_TRY(flags_get(ctx, 8, &d_small));              // [0] refusal flags, [2..5] the two 64-bit counts
     if (tie_rank) YA_TRY(ws_get(ctx, "sg_row_of_rank", static_cast<size_t>(n) * 4, (void**)&d_ror));
     YA_TRY(ws_get(ctx, "sg_part", static_cast<size_t>(S) * stripes * k * 8, (void**)&d_part));
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_small));
     auto* d_counts = reinterpret_cast<unsigned long long*>(d_small + 2);
 
-    YA_HIP(ctx, hipMemsetAsync(d_small, 0, 32, st));
     {
         TimedRegion tr(ctx, "semgraph_norm");
         YA_HIP(ctx, launch_semgraph_norm(st, rows, n, dim, d_inv, d_small));
         YA_HIP(ctx, launch_semgraph_check(st, n, tie_rank, source_rows, S, d_ror, d_small));
         tr.end();
     }
-    YA_HIP(ctx, hipMemcpyAsync(h_small, d_small, 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
+    YA_TRY(read_words(ctx, d_small, 1, h_small));
     if (h_small[0] & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, "a row holds a non-finite value or has an infinite inverse norm");
     if (h_small[0] & 2u) return fail(ctx, YAMS_ERR_INVALID_ARG, "a source index is out of range");
     if (h_small[0] & 4u) return fail(ctx, YAMS_ERR_INVALID_ARG, "tie_rank is not a permutation of [0, n)");
@@ -100,8 +84,7 @@ extern "C" yams_status_t yams_graph_semantic_neighbors_device(yams_accel_ctx* ct
         tr.end();
     }
     if (out_inv_norm) YA_HIP(ctx, hipMemcpyAsync(out_inv_norm, d_inv, static_cast<size_t>(n) * 4, hipMemcpyDeviceToDevice, st));
-    YA_HIP(ctx, hipMemcpyAsync(h_small, d_small, 32, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
+    YA_TRY(read_words(ctx, d_small, 8, h_small));
     if (out_diag) {
         out_diag->stripes = stripes;
         out_diag->source_tiles = source_tiles;

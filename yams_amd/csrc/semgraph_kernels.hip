@@ -29,6 +29,7 @@
 #include "common.h"
 #include "fp64_tile.h"
 #include "row_walk.h"
+#include "semgraph_launch.h"
 
 namespace yams_accel {
 

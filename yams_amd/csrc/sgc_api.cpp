@@ -7,19 +7,10 @@
 #include <cstring>
 
 #include "accel_ctx.h"
+#include "arg_checks.h"
+#include "sgc_launch.h"
 
 using namespace yams_accel;
-
-namespace yams_accel { // sgc_kernels.hip
-hipError_t launch_sgc_check(hipStream_t st, const float* x, uint64_t n, uint32_t dim, const uint64_t* off, const uint32_t* cols,
-                            const float* w, double* inv, uint32_t* hub_rows, uint32_t* small);
-hipError_t launch_sgc_scale(hipStream_t st, uint64_t n, const uint64_t* off, const uint32_t* cols, const float* w, const double* inv,
-                            double* scale, uint32_t* small);
-uint64_t sgc_hop_blocks(uint64_t n, uint32_t dim);
-bool sgc_vec_loads(uint32_t dim, const float* a, const float* b, const float* c);
-hipError_t launch_sgc_hop(hipStream_t st, const float* x, float* y, uint64_t n, uint32_t dim, const uint64_t* off, const uint32_t* cols,
-                          const double* scale, const double* inv, const uint32_t* hub_rows, uint32_t n_hubs, bool vec);
-}
 
 namespace {
 
@@ -34,8 +25,8 @@ yams_status_t check_args(yams_accel_ctx* ctx, const float* rows, uint64_t n, uin
     if (n == 0) { *done = true; return YAMS_OK; }
     if (dim == 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "dim == 0");
     if (!rows || !out || !row_offsets) return fail(ctx, YAMS_ERR_INVALID_ARG, "null rows, out or row_offsets");
-    const uintptr_t a = reinterpret_cast<uintptr_t>(rows), b = reinterpret_cast<uintptr_t>(out), bytes = static_cast<uintptr_t>(n) * dim * 4;
-    if (a < b + bytes && b < a + bytes) return fail(ctx, YAMS_ERR_INVALID_ARG, "out overlaps rows");
+    const size_t bytes = static_cast<size_t>(n) * dim * 4;
+    if (overlaps(rows, bytes, out, bytes)) return fail(ctx, YAMS_ERR_INVALID_ARG, "out overlaps rows");
     return YAMS_OK;
 }
 
@@ -59,19 +50,16 @@ extern "C" yams_status_t yams_graph_sgc_smooth_device(yams_accel_ctx* ctx, const
         return YAMS_OK;
     }
 
-    double* d_inv; uint32_t* d_hubs; uint32_t* d_small; uint32_t* h_small;
+    double* d_inv; uint32_t* d_hubs; uint32_t* d_small; uint32_t h_small[8];
     YA_TRY(ws_get(ctx, "sgc_inv", static_cast<size_t>(n) * 8, (void**)&d_inv));
     YA_TRY(ws_get(ctx, "sgc_hub_rows", static_cast<size_t>(n) * 4, (void**)&d_hubs));
-    YA_TRY(ws_get(ctx, "sgc_small", 32, (void**)&d_small));      // [0] flags [1] hub rows [2..3] nnz [4] max degree [6..7] zero-scale edges
-    YA_TRY(pinned_get(ctx, 64, (void**)&h_small));
-    YA_HIP(ctx, hipMemsetAsync(d_small, 0, 32, st));
+    YA_TRY(flags_get(ctx, 8, &d_small));      // [0] flags [1] hub rows [2..3] nnz [4] max degree [6..7] zero-scale edges
     {
         TimedRegion tr(ctx, "sgc_check");
         YA_HIP(ctx, launch_sgc_check(st, rows, n, dim, row_offsets, cols, weights, d_inv, d_hubs, d_small));
         tr.end();
     }
-    YA_HIP(ctx, hipMemcpyAsync(h_small, d_small, 32, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
+    YA_TRY(read_words(ctx, d_small, 8, h_small));
     const uint32_t flags = h_small[0], n_hubs = h_small[1], max_degree = h_small[4];
     uint64_t nnz;
     std::memcpy(&nnz, h_small + 2, 8);
@@ -100,8 +88,7 @@ extern "C" yams_status_t yams_graph_sgc_smooth_device(yams_accel_ctx* ctx, const
         }
         tr.end();
     }
-    YA_HIP(ctx, hipMemcpyAsync(h_small, d_small, 32, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
+    YA_TRY(read_words(ctx, d_small, 8, h_small));
     if (out_diag) {
         out_diag->nnz = nnz;
         std::memcpy(&out_diag->edges_skipped_zero_scale, h_small + 6, 8);
@@ -126,9 +113,7 @@ extern "C" yams_status_t yams_graph_sgc_smooth_host(yams_accel_ctx* ctx, const f
         return YAMS_OK;
     }
     // the offsets size the uploads: they are judged here first
-    if (row_offsets[0] != 0) return fail(ctx, YAMS_ERR_INVALID_ARG, "row_offsets does not start at 0 or decreases");
-    for (uint64_t i = 0; i < n; ++i)
-        if (row_offsets[i + 1] < row_offsets[i]) return fail(ctx, YAMS_ERR_INVALID_ARG, "row_offsets does not start at 0 or decreases");
+    if (!offsets_ascend(row_offsets, n)) return fail(ctx, YAMS_ERR_INVALID_ARG, "row_offsets does not start at 0 or decreases");
     const uint64_t nnz = row_offsets[n];
     if (nnz >= (1ull << 32)) return fail(ctx, YAMS_ERR_UNSUPPORTED, "nnz must be < 2^32");
     if (nnz && (!cols || !weights)) return fail(ctx, YAMS_ERR_INVALID_ARG, "null cols or weights");

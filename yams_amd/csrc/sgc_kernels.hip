@@ -26,6 +26,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "sgc_launch.h"
 
 namespace yams_accel {
 
@@ -200,7 +201,6 @@ __global__ __launch_bounds__(kSgcThreads) void sgc_hop_kernel(const float* __res
 // ---- launchers ------------------------------------------------------------------------------------------------------------
 static inline uint32_t sgc_blocks(uint64_t n, uint32_t per) { return static_cast<uint32_t>((n + per - 1) / per); }
 
-// The checks and the degrees.  small: 8 zeroed words (the layout above); hub_rows: [n] uint32.
 hipError_t launch_sgc_check(hipStream_t st, const float* x, uint64_t n, uint32_t dim, const uint64_t* off, const uint32_t* cols,
                             const float* w, double* inv, uint32_t* hub_rows, uint32_t* small) {
     sgc_offsets_kernel<<<sgc_blocks(n, kSgcThreads), kSgcThreads, 0, st>>>(off, n, small);
@@ -226,14 +226,12 @@ static uint64_t sgc_hop_grid(uint64_t rows, uint32_t cpr) {
     return rows * ((cpr + kSgcThreads - 1) / kSgcThreads);
 }
 
-// The number of workgroups of the main launch of one hop (the caller refuses a grid beyond the launch limit).
 uint64_t sgc_hop_blocks(uint64_t n, uint32_t dim) { return sgc_hop_grid(n, (dim + 3) / 4); }
 
 bool sgc_vec_loads(uint32_t dim, const float* a, const float* b, const float* c) {
     return dim % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
-// One hop x -> y.  vec: sgc_vec_loads over every buffer the hops of this call touch.
 hipError_t launch_sgc_hop(hipStream_t st, const float* x, float* y, uint64_t n, uint32_t dim, const uint64_t* off, const uint32_t* cols,
                           const double* scale, const double* inv, const uint32_t* hub_rows, uint32_t n_hubs, bool vec) {
     const uint32_t blocks = static_cast<uint32_t>(sgc_hop_blocks(n, dim));
