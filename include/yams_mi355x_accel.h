@@ -1132,8 +1132,10 @@ YAMS_ACCEL_API yams_status_t yams_features_compose_host(
  * Limits: dim <= YAMS_RERANK_MAX_DIM, tq <= YAMS_RERANK_MAX_QUERY_TOKENS, n_docs <= YAMS_RERANK_MAX_DOCS, n_docs * tq <=
  * YAMS_RERANK_MAX_ROWMAX, a document <= YAMS_RERANK_MAX_DOC_TOKENS rows, the pool <= YAMS_RERANK_MAX_ROWS rows: beyond,
  * YAMS_ERR_UNSUPPORTED.  dim == 0, a null array that is needed, offsets that do not start at 0 or decrease, an unknown form, an
- * output overlapping an input: YAMS_ERR_INVALID_ARG.  Every refusal is found before anything is written.  Every call
- * synchronises the context's stream before returning.  The _host twins take host arrays throughout. */
+ * output overlapping an input: YAMS_ERR_INVALID_ARG.  Order, in both twins: the limits that need no array, then the nulls and the
+ * form, then the OFFSETS (their defects, a document too long), and only then what the offsets' total sizes — the row limit, null
+ * rows, the overlaps: a call with two defects reports the earlier one.  Every refusal is found before anything is written.  Every
+ * call synchronises the context's stream before returning.  The _host twins take host arrays throughout. */
 #define YAMS_RERANK_MAX_DIM 1024u
 #define YAMS_RERANK_MAX_DOC_TOKENS (1u << 20)
 #define YAMS_RERANK_MAX_QUERY_TOKENS (1u << 16)
@@ -1171,6 +1173,66 @@ YAMS_ACCEL_API yams_status_t yams_rerank_maxpool_device(
     yams_accel_ctx* ctx, const float* rows, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, float* out);
 YAMS_ACCEL_API yams_status_t yams_rerank_maxpool_host(
     yams_accel_ctx* ctx, const float* rows, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, float* out);
+
+/* ------------------------------------------------------------------------------------------ */
+/* The embedding model's pooling head: CLS, max or mean over the tokens of each text            */
+/* ------------------------------------------------------------------------------------------ */
+/* Every embedding the reference produces passes through the pooling head of its ONNX plugin: OnnxModelSession takes the
+ * encoder's output [B, S, D] (fp32 hidden states) and the attention masks and, on one host core, pools the tokens of each text
+ * and L2-normalises the result (plugins/onnx/onnx_model_pool.cpp:1808-1854 the batch path; :1729-1774 and :1448-1491 the same
+ * loops; :1935-1953, :1501-1515 and :1888-1900 the rank-2 output, which is normalised only).  These entries are those loops;
+ * the shell that flattens the masks and keeps the host's own loop for what is refused is include/yams_accel/embedding_pool.hpp.
+ * The contract, restated.  Per text b, with T = min(seq, mask_len) tokens considered:
+ *   start      emb[dim] starts at +0.0f.
+ *   CLS        emb[d] = hidden[b][0][d], whatever the mask says (the mask is never read; the diag's counts are 0).
+ *   MAX        for each token i < T with mask[b][i] > 0, in token order: emb[d] = (emb[d] < x) ? x : emb[d] (std::max: a NaN
+ *              never enters; the floor is the initial +0.0f).  Any positive mask value is active.
+ *   MEAN       total = 0.0f; for each i < T with w = float(mask[b][i]) > 0: total += w; emb[d] += x * w — ONE fp32 chain per
+ *              (b, d) in token order, never split or reassociated; then, if total > 0, emb[d] = emb[d] / total, a correctly
+ *              rounded fp32 division.  Served for masks of 0 and 1 (what the reference's generateAttentionMask produces): the
+ *              product is then exact and the fused and the separate host build agree.  A considered value above 1 is refused.
+ *   normalise  (YAMS_EMBED_NORMALIZE) norm = sqrt of ONE fp64 chain of double(v) * double(v) in element order (exact products:
+ *              form-free); norm > 1e-8: v = float(double(v) / norm), otherwise a row of zeros — a NaN norm fails the comparison.
+ * A masked row is never read: a NaN or an infinity there does not reach the output.  Subnormals are kept.  Results equal the CPU
+ * loop bit for bit; a NaN is some NaN.
+ * Limits: dim <= YAMS_EMBED_MAX_DIM, seq <= YAMS_EMBED_MAX_SEQ, batch * seq <= YAMS_EMBED_MAX_ROWS (normalise: batch <=
+ * YAMS_EMBED_MAX_ROWS), MEAN with a considered mask value above 1: beyond, YAMS_ERR_UNSUPPORTED.  dim == 0, seq == 0, a null
+ * array that is needed, an unknown mode or flag bit, an output overlapping an input: YAMS_ERR_INVALID_ARG.  Every refusal is
+ * found before anything is written.  Every call synchronises the context's stream before returning.  The _host twins take host
+ * arrays throughout. */
+#define YAMS_EMBED_MAX_DIM 8192u
+#define YAMS_EMBED_MAX_SEQ (1u << 16)
+#define YAMS_EMBED_MAX_ROWS (1ull << 22)
+#define YAMS_EMBED_POOL_CLS 0u
+#define YAMS_EMBED_POOL_MAX 1u
+#define YAMS_EMBED_POOL_MEAN 2u
+#define YAMS_EMBED_NORMALIZE 1u /* flags: L2-normalise the pooled rows */
+typedef struct yams_embed_diag {
+    uint32_t mode;              /* the mode asked for */
+    uint32_t flags;             /* the flags asked for */
+    uint64_t batch;             /* texts seen */
+    uint32_t seq;               /* tokens per text */
+    uint32_t dim;
+    uint64_t tokens_considered; /* batch * min(seq, mask_len); 0 for CLS or without a mask */
+    uint64_t active_tokens;     /* considered mask values above 0; 0 for CLS */
+    uint32_t slab_dims;         /* dimensions one workgroup owned: chosen from batch and dim so that small batches cover the device */
+    uint32_t reserved;
+} yams_embed_diag_t;
+/* The pooled (and, when asked, normalised) row of every text.
+ *   hidden   [batch][seq][dim] fp32
+ *   mask     [batch][mask_len] int32; nullable for CLS or when mask_len == 0 (MAX and MEAN then give zeros)
+ *   out      [batch][dim] fp32
+ *   diag     nullable, written on YAMS_OK
+ * batch == 0: YAMS_OK, nothing written. */
+YAMS_ACCEL_API yams_status_t yams_embed_pool_device(
+    yams_accel_ctx* ctx, const float* hidden, uint64_t batch, uint32_t seq, uint32_t dim, const int32_t* mask, uint32_t mask_len,
+    uint32_t mode, uint32_t flags, float* out, yams_embed_diag_t* diag);
+YAMS_ACCEL_API yams_status_t yams_embed_pool_host(
+    yams_accel_ctx* ctx, const float* hidden, uint64_t batch, uint32_t seq, uint32_t dim, const int32_t* mask, uint32_t mask_len,
+    uint32_t mode, uint32_t flags, float* out, yams_embed_diag_t* diag);
+/* The rank-2 output: out[b][:] = rows[b][:] L2-normalised.  rows, out [batch][dim] fp32.  batch == 0: YAMS_OK, nothing written. */
+YAMS_ACCEL_API yams_status_t yams_embed_normalize_device(yams_accel_ctx* ctx, const float* rows, uint64_t batch, uint32_t dim, float* out);
+YAMS_ACCEL_API yams_status_t yams_embed_normalize_host(yams_accel_ctx* ctx, const float* rows, uint64_t batch, uint32_t dim, float* out);
 
 /* ------------------------------------------------------------------------------------------ */
 /* The semantic-neighbour graph: exact top-K self-join of the document-level embeddings         */
@@ -1834,6 +1896,28 @@ typedef struct yams_late_interaction_rerank_v1 {
     /* out: the caller's [n_docs][dim] */
     yams_status_t (*maxpool)(void* self, const float* rows, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, float* out);
 } yams_late_interaction_rerank_v1;
+
+/* The embedding model's pooling head (yams_embed_pool_* / yams_embed_normalize_*).  A separate interface, version 1, served by
+ * yams_plugin_get_interface and NOT listed in the manifest, for the reason given at vector_doc_scan_v1.  pool and normalize take
+ * host memory in and give host memory out: every output is the caller's array.  pool_device and normalize_device take the
+ * hidden states (the rows) at a DEVICE address of the plugin's device (an encoder whose output is bound to device memory) and
+ * everything else in host memory: only the masks and the batch * dim result cross the bus.  Statuses and limits of the flat
+ * entries. */
+#define YAMS_IFACE_EMBEDDING_POOL_V1 "embedding_pool_v1"
+#define YAMS_IFACE_EMBEDDING_POOL_V1_VERSION 1u
+typedef struct yams_embedding_pool_v1 {
+    uint32_t abi_version; /* YAMS_IFACE_EMBEDDING_POOL_V1_VERSION */
+    void* self;
+    /* out: the caller's [batch][dim]; mask: nullable for CLS or mask_len == 0; diag: nullable */
+    yams_status_t (*pool)(void* self, const float* hidden, uint64_t batch, uint32_t seq, uint32_t dim, const int32_t* mask,
+                          uint32_t mask_len, uint32_t mode, uint32_t flags, float* out, yams_embed_diag_t* diag);
+    /* out: the caller's [batch][dim] */
+    yams_status_t (*normalize)(void* self, const float* rows, uint64_t batch, uint32_t dim, float* out);
+    /* hidden / rows: device addresses; mask, out, diag: the caller's host arrays */
+    yams_status_t (*pool_device)(void* self, const float* hidden, uint64_t batch, uint32_t seq, uint32_t dim, const int32_t* mask,
+                                 uint32_t mask_len, uint32_t mode, uint32_t flags, float* out, yams_embed_diag_t* diag);
+    yams_status_t (*normalize_device)(void* self, const float* rows, uint64_t batch, uint32_t dim, float* out);
+} yams_embedding_pool_v1;
 
 /* WHAT THE DEVICE IS WORSE AT IS REFUSED, NOT SERVED SLOWLY.  SHA-256 of one message is one sequential chain: a
  * GPU lane advances it at ~35 MB/s, a host core with SHA-NI at > 1 GB/s.  The device wins only with many

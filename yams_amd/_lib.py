@@ -341,6 +341,32 @@ class LateInteractionRerankV1(C.Structure):  # late_interaction_rerank_v1 (serve
     ]
 
 
+# YAMS_EMBED_MAX_* / YAMS_EMBED_POOL_* / YAMS_EMBED_NORMALIZE
+EMBED_MAX_DIM, EMBED_MAX_SEQ, EMBED_MAX_ROWS = 8192, 1 << 16, 1 << 22
+EMBED_POOL_CLS, EMBED_POOL_MAX, EMBED_POOL_MEAN, EMBED_NORMALIZE = 0, 1, 2, 1
+EMBED_SLAB_DIMS, EMBED_MIN_SLAB_DIMS, EMBED_WINDOW = 256, 64, 128     # embed_launch.h: the kernel's edges (the tests' lattice)
+IFACE_EMBEDDING_POOL_V1 = "embedding_pool_v1"
+
+
+class EmbedDiag(C.Structure):  # yams_embed_diag_t
+    _fields_ = [("mode", C.c_uint32), ("flags", C.c_uint32), ("batch", C.c_uint64), ("seq", C.c_uint32), ("dim", C.c_uint32),
+                ("tokens_considered", C.c_uint64), ("active_tokens", C.c_uint64), ("slab_dims", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_EMBED_POOL = [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(EmbedDiag)]
+_EMBED_NORMALIZE = [vp, C.c_uint64, C.c_uint32, vp]
+
+
+class EmbeddingPoolV1(C.Structure):  # embedding_pool_v1 (served by get_interface, not listed in the manifest)
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("self", vp),
+        ("pool", C.CFUNCTYPE(C.c_int, vp, *_EMBED_POOL)),
+        ("normalize", C.CFUNCTYPE(C.c_int, vp, *_EMBED_NORMALIZE)),
+        ("pool_device", C.CFUNCTYPE(C.c_int, vp, *_EMBED_POOL)),
+        ("normalize_device", C.CFUNCTYPE(C.c_int, vp, *_EMBED_NORMALIZE)),
+    ]
+
+
 class ContentHashV1(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("self", vp),
@@ -418,6 +444,7 @@ EXPORTS = [
     "yams_features_aggregate_device", "yams_features_aggregate_host", "yams_features_variance_device", "yams_features_variance_host",
     "yams_features_compose_device", "yams_features_compose_host",
     "yams_rerank_maxsim_device", "yams_rerank_maxsim_host", "yams_rerank_maxpool_device", "yams_rerank_maxpool_host",
+    "yams_embed_pool_device", "yams_embed_pool_host", "yams_embed_normalize_device", "yams_embed_normalize_host",
     "yams_scan_build_shadow_device", "yams_scan_build_shadow_i8_device", "yams_scan_build_shadow_i8_layout_device", "yams_scan_choose_i8_layout_device",
     "yams_scan_record_layout", "yams_scan_merge_records_device", "yams_scan_sharded_create",
     "yams_scan_sharded_destroy", "yams_scan_sharded_count", "yams_scan_sharded_ctx",
@@ -538,6 +565,10 @@ def load(share_torch_runtime: bool = True) -> C.CDLL:
         fn.argtypes = [vp, *_RERANK_MAXSIM]
     for fn in (L.yams_rerank_maxpool_device, L.yams_rerank_maxpool_host):
         fn.argtypes = [vp, *_RERANK_MAXPOOL]
+    for fn in (L.yams_embed_pool_device, L.yams_embed_pool_host):
+        fn.argtypes = [vp, *_EMBED_POOL]
+    for fn in (L.yams_embed_normalize_device, L.yams_embed_normalize_host):
+        fn.argtypes = [vp, *_EMBED_NORMALIZE]
     L.yams_scan_topk_host.argtypes = [vp, C.POINTER(ScanCorpus), vp, C.c_uint32,
                                       C.POINTER(ScanParams), vp, vp, vp, vp, C.POINTER(ScanDiag)]
     L.yams_scan_build_shadow_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]

@@ -932,6 +932,32 @@ class Accel:
             lambda i, o: (i[0], dim, i[1], d, o[0]), misalign)
         return out.reshape(d, dim)
 
+    # ---- the embedding model's pooling head (yams_embed_*) -----------------------------------------------------------------------
+    def embed_pool(self, hidden: np.ndarray, mask=None, mode: int = _lib.EMBED_POOL_MEAN, normalize: bool = True, host_entry: bool = False,
+                   misalign: int = 0):
+        """The pooled row of every text (yams_embed_pool_device / _host): hidden [batch][seq][dim] float32, mask [batch][mask_len]
+        int32 or None.  Returns (out [batch][dim] float32, diag dict)."""
+        x = np.ascontiguousarray(hidden, np.float32)
+        batch, seq, dim = x.shape
+        m = None if mask is None else np.ascontiguousarray(mask, np.int32).reshape(batch, -1)
+        mask_len = 0 if m is None else m.shape[1]
+        flags = _lib.EMBED_NORMALIZE if normalize else 0
+        dg = _lib.EmbedDiag()
+        out, = self._artifact_call(
+            self.L.yams_embed_pool_device, self.L.yams_embed_pool_host, host_entry,
+            [x if x.size else None, m if m is not None and m.size else None], [(np.float32, batch * dim)],
+            lambda i, o: (i[0], batch, seq, dim, i[1], mask_len, mode, flags, o[0], C.byref(dg)), misalign)
+        return out.reshape(batch, dim), {k: getattr(dg, k) for k, _ in _lib.EmbedDiag._fields_}
+
+    def embed_normalize(self, rows: np.ndarray, host_entry: bool = False, misalign: int = 0):
+        """The rank-2 output: every row L2-normalised (yams_embed_normalize_device / _host).  Returns out [batch][dim] float32."""
+        x = np.ascontiguousarray(rows, np.float32)
+        batch, dim = x.shape
+        out, = self._artifact_call(
+            self.L.yams_embed_normalize_device, self.L.yams_embed_normalize_host, host_entry,
+            [x if x.size else None], [(np.float32, batch * dim)], lambda i, o: (i[0], batch, dim, o[0]), misalign)
+        return out.reshape(batch, dim)
+
     # ---- cluster routing (yams_route_index_* / yams_route_dense_*) ----------------------------------------------------------
     def route_index(self, vectors: np.ndarray, cluster_offsets, has_centroid, position, host_entry: bool = False,
                     misalign: int = 0) -> "RouteIndex":

@@ -1,8 +1,8 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
 // Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// fourteen interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, topology_quality_v1, topology_features_v1, late_interaction_rerank_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
+// fifteen interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
+// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, topology_quality_v1, topology_features_v1, late_interaction_rerank_v1, embedding_pool_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
 // conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
 // this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
 // 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
@@ -1510,6 +1510,62 @@ yams_status_t lr_maxpool(void*, const float* rows, uint32_t dim, const uint64_t*
 
 yams_late_interaction_rerank_v1 g_late_rerank = {YAMS_IFACE_LATE_INTERACTION_RERANK_V1_VERSION, nullptr, GUARDED(lr_maxsim), GUARDED(lr_maxpool)};
 
+// ---- embedding_pool_v1: the embedding model's pooling head (yams_embed_*), over host memory or over device addresses -----------
+// every output is the caller's array: every check is the flat entry's
+yams_status_t ep_pool(void*, const float* hidden, uint64_t batch, uint32_t seq, uint32_t dim, const int32_t* mask, uint32_t mask_len,
+                      uint32_t mode, uint32_t flags, float* out, yams_embed_diag_t* diag) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    return yams_embed_pool_host(lease.v, hidden, batch, seq, dim, mask, mask_len, mode, flags, out, diag);
+}
+yams_status_t ep_normalize(void*, const float* rows, uint64_t batch, uint32_t dim, float* out) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    return yams_embed_normalize_host(lease.v, rows, batch, dim, out);
+}
+// the hidden states (the rows) at a DEVICE address, everything else in host memory: the mask goes up, the B * dim result comes back
+yams_status_t ep_pool_device(void*, const float* hidden, uint64_t batch, uint32_t seq, uint32_t dim, const int32_t* mask, uint32_t mask_len,
+                             uint32_t mode, uint32_t flags, float* out, yams_embed_diag_t* diag) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    yams_accel_ctx* ctx = lease.v;
+    // what the flat entry refuses (or, batch == 0, answers) before it looks at a mask or an output: its verdict, nothing is staged
+    if (batch == 0 || !out || dim == 0 || seq == 0 || dim > YAMS_EMBED_MAX_DIM || seq > YAMS_EMBED_MAX_SEQ || batch > YAMS_EMBED_MAX_ROWS / seq)
+        return yams_embed_pool_device(ctx, hidden, batch, seq, dim, nullptr, mask_len, mode, flags, out, diag);
+    // only the considered columns of the mask go up: at most batch * seq values
+    if (mode == YAMS_EMBED_POOL_CLS) mask = nullptr;
+    const uint32_t cols = mask_len < seq ? mask_len : seq;
+    const size_t mb = mask ? static_cast<size_t>(batch) * cols * 4 : 0, ob = static_cast<size_t>(batch) * dim * 4;
+    int32_t* d_mask = nullptr; float* d_out;
+    if (mb) YA_TRY(yams_accel::ws_get(ctx, "embed_door_mask", mb, (void**)&d_mask));
+    YA_TRY(yams_accel::ws_get(ctx, "embed_door_out", ob, (void**)&d_out));
+    if (mb && cols == mask_len) YA_HIP(ctx, yams_accel::staged_h2d(d_mask, mask, mb, ctx->stream));
+    else if (mb) YA_HIP(ctx, hipMemcpy2DAsync(d_mask, static_cast<size_t>(cols) * 4, mask, static_cast<size_t>(mask_len) * 4, static_cast<size_t>(cols) * 4, batch, hipMemcpyHostToDevice, ctx->stream));
+    if (mask && !mb) mask_len = 0;
+    else if (mask) mask_len = cols;
+    YA_TRY(yams_embed_pool_device(ctx, hidden, batch, seq, dim, d_mask, mask_len, mode, flags, d_out, diag));
+    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
+    YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return YAMS_OK;
+}
+yams_status_t ep_normalize_device(void*, const float* rows, uint64_t batch, uint32_t dim, float* out) {
+    NEED_INIT();
+    Lease<yams_accel_ctx*> lease(g.work_ctx);
+    yams_accel_ctx* ctx = lease.v;
+    if (batch == 0 || !out || dim == 0 || dim > YAMS_EMBED_MAX_DIM || batch > YAMS_EMBED_MAX_ROWS)
+        return yams_embed_normalize_device(ctx, rows, batch, dim, out);      // its verdict; nothing is staged
+    const size_t ob = static_cast<size_t>(batch) * dim * 4;
+    float* d_out;
+    YA_TRY(yams_accel::ws_get(ctx, "embed_door_out", ob, (void**)&d_out));
+    YA_TRY(yams_embed_normalize_device(ctx, rows, batch, dim, d_out));
+    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
+    YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return YAMS_OK;
+}
+
+yams_embedding_pool_v1 g_embedding_pool = {YAMS_IFACE_EMBEDDING_POOL_V1_VERSION, nullptr, GUARDED(ep_pool), GUARDED(ep_normalize),
+                                           GUARDED(ep_pool_device), GUARDED(ep_normalize_device)};
+
 // ---- content_checksum_v1: the compressed store's CRC-32 over host memory (yams_crc32_many_host) ------------------------------
 yams_status_t cs_crc32_many(void*, const uint8_t* const* msgs, const size_t* lens, size_t n, uint32_t* out) {
     NEED_INIT();
@@ -1795,6 +1851,7 @@ int yams_plugin_get_interface(const char* iface_id, uint32_t version, void** out
         {YAMS_IFACE_TOPOLOGY_QUALITY_V1, YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION, &g_topology_quality},
         {YAMS_IFACE_TOPOLOGY_FEATURES_V1, YAMS_IFACE_TOPOLOGY_FEATURES_V1_VERSION, &g_topology_features},
         {YAMS_IFACE_LATE_INTERACTION_RERANK_V1, YAMS_IFACE_LATE_INTERACTION_RERANK_V1_VERSION, &g_late_rerank},
+        {YAMS_IFACE_EMBEDDING_POOL_V1, YAMS_IFACE_EMBEDDING_POOL_V1_VERSION, &g_embedding_pool},
         {YAMS_IFACE_CONTENT_HASH_V1, YAMS_IFACE_CONTENT_HASH_V1_VERSION, &g_content_hash},
         {YAMS_IFACE_CONTENT_CHECKSUM_V1, YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, &g_content_checksum},
         {YAMS_IFACE_CHUNKER_V1, YAMS_IFACE_CHUNKER_V1_VERSION, &g_chunker}};

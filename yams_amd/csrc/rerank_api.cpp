@@ -1,7 +1,7 @@
 // rerank_api.cpp — yams_rerank_maxsim / yams_rerank_maxpool (_device and _host): OnnxColbertSession's computeMaxSim over a
 // window of candidate documents, and maxPoolEmbeddings + normalizeEmbedding, behind the C ABI.  Every entry: the limits (no
-// device needed) -> argument checks -> the pool's total read back -> ONE read-back of the check flags -> the work.  Nothing is
-// written to an output before every refusal is known.
+// device needed) -> argument checks -> the pool's total read back -> ONE read-back of the check flags (the offsets' verdict) ->
+// what the total sizes (the row limit, the overlaps) -> the work.  Nothing is written to an output before every refusal is known.
 #include <cstdlib>
 #include <cstring>
 
@@ -100,8 +100,8 @@ extern "C" yams_status_t yams_rerank_maxsim_device(yams_accel_ctx* ctx, const fl
     hipStream_t st = ctx->stream;
     uint64_t total;
     YA_TRY(read_words(ctx, doc_offsets + n_docs, 2, &total));
+    YA_TRY(device_check(ctx, doc_offsets, n_docs, total));      // the offsets first, as the host twin judges them: what they claim sizes the overlap test
     YA_TRY(check_maxsim_total(ctx, query, tq, dim, rows, total, n_docs, out_scores, out_rowmax));
-    YA_TRY(device_check(ctx, doc_offsets, n_docs, total));
     const bool fused = form == YAMS_RESIDUAL_FUSED;
     const RerankPath path = fused ? fused_path() : kRerankValu;
     float* d_rowmax = out_rowmax;
@@ -170,8 +170,8 @@ extern "C" yams_status_t yams_rerank_maxpool_device(yams_accel_ctx* ctx, const f
     hipStream_t st = ctx->stream;
     uint64_t total;
     YA_TRY(read_words(ctx, doc_offsets + n_docs, 2, &total));
-    YA_TRY(check_maxpool_total(ctx, dim, rows, total, n_docs, out));
     YA_TRY(device_check(ctx, doc_offsets, n_docs, total));
+    YA_TRY(check_maxpool_total(ctx, dim, rows, total, n_docs, out));
     {
         TimedRegion tr(ctx, "rerank_maxpool");
         YA_HIP(ctx, launch_rerank_maxpool(st, rows, dim, doc_offsets, static_cast<uint32_t>(n_docs), out));

@@ -37,6 +37,7 @@
 // f32 denormals.
 #include "common.h"
 #include "form_step.h"
+#include "l2_normalize.h"
 #include "rerank_launch.h"
 
 namespace yams_accel {
@@ -237,18 +238,10 @@ __global__ __launch_bounds__(kRerankThreads) void rerank_maxpool_kernel(const fl
         s_p[d] = p;
     }
     __syncthreads();
-    if (t == 0) {
-        double nsq = 0.0;
-        for (uint32_t d = 0; d < dim; ++d) {
-            const double v = static_cast<double>(s_p[d]);
-            nsq = __dadd_rn(nsq, __dmul_rn(v, v));              // exact products: form-free
-        }
-        s_norm = __dsqrt_rn(nsq);
-    }
+    if (t == 0) s_norm = l2_norm(l2_chain(0.0, s_p, dim));      // l2_normalize.h: one lane, element order
     __syncthreads();
     const double norm = s_norm;
-    for (uint32_t d = t; d < dim; d += kRerankThreads)
-        out[static_cast<uint64_t>(doc) * dim + d] = norm > 1e-8 ? static_cast<float>(__ddiv_rn(static_cast<double>(s_p[d]), norm)) : 0.0f;
+    for (uint32_t d = t; d < dim; d += kRerankThreads) out[static_cast<uint64_t>(doc) * dim + d] = l2_quotient(s_p[d], norm);
 }
 
 __global__ __launch_bounds__(256) void rerank_check_kernel(const uint64_t* __restrict__ off, uint64_t n_docs, uint64_t total,
