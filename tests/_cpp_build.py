@@ -107,24 +107,34 @@ def build_contract_rules_test():
     return exe
 
 
-def build_plugin_host_test():
-    """Compiles tests/cpp/plugin_host_test.cpp (plain g++, no GPU, no ROCm include path: yams_amd/csrc/plugin_host.h is the
-    plugin door's host logic) with AddressSanitizer and UBSan: the program has its own main and hands the header heap
-    arrays of exactly the contracted lengths, so an access past one ends the run.  Returns the executable."""
+def _plugin_host_test(exe_name, flags):
     out_dir = os.path.join(ROOT, "tests", "cpp", "_build")
     os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "plugin_host_test")
+    exe = os.path.join(out_dir, exe_name)
     src = os.path.join(ROOT, "tests", "cpp", "plugin_host_test.cpp")
     deps = [src, os.path.join(ROOT, "include", "yams_mi355x_accel.h")] + \
         [os.path.join(ROOT, "yams_amd", "csrc", h) for h in ("plugin_host.h", "contract_rules.h")]
     if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
         return exe
-    r = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra",
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    r = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", *flags, "-o", exe, src,
+                        "-lpthread"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     if r.returncode != 0:
-        raise RuntimeError("plugin_host_test failed to compile:\n" + r.stdout.decode())
+        raise RuntimeError(exe_name + " failed to compile:\n" + r.stdout.decode())
     return exe
+
+
+def build_plugin_host_test():
+    """Compiles tests/cpp/plugin_host_test.cpp (plain g++, no GPU, no ROCm include path: yams_amd/csrc/plugin_host.h is the
+    plugin door's host logic, its ownership and registry rules included) with AddressSanitizer and UBSan: the program has its
+    own main and hands the header heap arrays of exactly the contracted lengths, so an access past one ends the run, and an
+    array that is neither handed out nor freed fails it at exit.  Returns the executable."""
+    return _plugin_host_test("plugin_host_test", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+
+
+def build_plugin_host_test_tsan():
+    """The same stand-alone program with ThreadSanitizer (host code only), for its --threads mode: eight threads on one
+    HandleTable.  Returns the executable."""
+    return _plugin_host_test("plugin_host_test_tsan", ["-fsanitize=thread"])
 
 
 def build_arg_checks_test():

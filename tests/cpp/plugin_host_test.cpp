@@ -4,11 +4,14 @@
 // a heap array of exactly the length its contract states, so a read or write past the contract fails the run.
 //
 //   plugin_host_test           runs every case, prints one line per failure and "OK (0 failures)"
+//   plugin_host_test --threads eight threads on one HandleTable, nothing else (the -fsanitize=thread build runs only this)
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <random>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../yams_amd/csrc/plugin_host.h"
@@ -275,9 +278,164 @@ void test_config() {
     }
 }
 
+// ---- HandleTable: the registry of a handle family -------------------------------------------------------------------------------
+struct Thing {                   // an entry as the door keeps them: its own mutex, a payload that its taker destroys under it
+    std::mutex mu;
+    int* payload;
+    std::atomic<int>* destroyed; // how often this entry's payload was destroyed
+    Thing(int v, std::atomic<int>* d) : payload(new int(v)), destroyed(d) {}
+    ~Thing() { delete payload; } // (an entry that was never destroyed still gives its payload back: the test leaks nothing)
+    void destroy() { if (payload) { delete payload; payload = nullptr; ++*destroyed; } }
+};
+
+void test_handle_table() {
+    std::atomic<int> destroyed{0};
+    HandleTable<Thing> t;
+    CHECK(t.size() == 0 && !t.find(0) && !t.find(1) && !t.take(1), "an empty table knows an id");
+    const uint64_t a = t.insert(std::make_shared<Thing>(10, &destroyed)), b = t.insert(std::make_shared<Thing>(20, &destroyed)),
+                   c = t.insert(std::make_shared<Thing>(30, &destroyed));
+    CHECK(a == 1 && b == 2 && c == 3 && t.size() == 3, "ids %llu %llu %llu", (unsigned long long)a, (unsigned long long)b, (unsigned long long)c);
+    CHECK(t.find(b) && *t.find(b)->payload == 20 && !t.find(4) && !t.find(0) && !t.take(4) && !t.take(~0ull), "find / take of unknown ids");
+    {   // a call that found the entry before the destroy: the entry outlives take(), its payload reads as destroyed
+        const std::shared_ptr<Thing> held = t.find(b);
+        const std::shared_ptr<Thing> taken = t.take(b);
+        CHECK(taken && taken == held, "take() does not hand out the entry find() found");
+        CHECK(!t.find(b) && !t.take(b) && t.size() == 2, "a taken id is still known");
+        { std::lock_guard<std::mutex> lk(taken->mu); taken->destroy(); }
+        std::lock_guard<std::mutex> lk(held->mu);
+        CHECK(held->payload == nullptr && destroyed == 1, "the holder does not see the destroy");
+    }
+    const uint64_t d = t.insert(std::make_shared<Thing>(40, &destroyed));
+    CHECK(d == 4, "the id of a taken entry is reused: %llu", (unsigned long long)d);
+    std::vector<int> seen;
+    t.visit([&](const Thing& e) { seen.push_back(*e.payload); });
+    CHECK((seen == std::vector<int>{10, 30, 40}), "visit() walks %zu entries", seen.size());
+    seen.clear();
+    t.drain([&](Thing& e) { seen.push_back(*e.payload); e.destroy(); });
+    CHECK((seen == std::vector<int>{10, 30, 40}) && destroyed == 4, "drain() visits every entry once: %zu visits, %d destroyed", seen.size(), destroyed.load());
+    CHECK(t.size() == 0 && !t.find(a) && !t.find(c) && !t.find(d), "the table is not empty after drain()");
+    t.drain([&](Thing&) { CHECK(false, "a drained table still holds an entry"); });
+    const uint64_t e = t.insert(std::make_shared<Thing>(50, &destroyed));      // ids go on across a shutdown and a fresh init
+    CHECK(e == 5 && *t.find(e)->payload == 50, "after drain() the ids start again: %llu", (unsigned long long)e);
+}
+
+// Eight threads on one table: insert, find-and-use, take-and-destroy, mixed; then the teardown walk.  Every entry that was ever
+// inserted has been destroyed exactly once at the end — by the thread that took it or by drain() — and no use of a found entry
+// touched a payload outside its mutex.
+int run_threads() {
+    constexpr int kThreads = 8, kOps = 4000;
+    std::vector<std::atomic<int>> destroyed(kThreads * kOps);
+    for (auto& d : destroyed) d = 0;
+    std::atomic<uint64_t> inserted{0}, high{0};
+    HandleTable<Thing> t;
+    std::vector<std::thread> threads;
+    for (int w = 0; w < kThreads; ++w)
+        threads.emplace_back([&, w] {
+            std::mt19937_64 rng(1000 + w);
+            for (int op = 0; op < kOps; ++op) {
+                const uint64_t known = high.load();
+                const uint64_t id = known ? 1 + rng() % known : 1;
+                switch (rng() % 4) {
+                    case 0: {
+                        const uint64_t slot = inserted++;
+                        const uint64_t got = t.insert(std::make_shared<Thing>(static_cast<int>(slot), &destroyed[slot]));
+                        uint64_t h = high.load();
+                        while (h < got && !high.compare_exchange_weak(h, got)) {}
+                        break;
+                    }
+                    case 1: case 2:
+                        if (const std::shared_ptr<Thing> e = t.find(id)) {
+                            std::lock_guard<std::mutex> lk(e->mu);
+                            if (e->payload) CHECK(*e->payload >= 0, "a live payload reads %d", *e->payload);
+                        }
+                        break;
+                    default:
+                        if (const std::shared_ptr<Thing> e = t.take(id)) {
+                            std::lock_guard<std::mutex> lk(e->mu);
+                            e->destroy();
+                        }
+                }
+            }
+        });
+    for (auto& th : threads) th.join();
+    CHECK(high.load() == inserted.load(), "%llu ids for %llu entries", (unsigned long long)high.load(), (unsigned long long)inserted.load());
+    t.drain([](Thing& e) { e.destroy(); });
+    CHECK(t.size() == 0, "entries after drain()");
+    int wrong = 0;
+    for (uint64_t i = 0; i < inserted; ++i) wrong += destroyed[i] != 1;
+    CHECK(wrong == 0 && inserted > 0, "%d of %llu entries were not destroyed exactly once", wrong, (unsigned long long)inserted.load());
+    if (g_failures == 0) std::printf("threads OK (0 failures, %llu entries)\n", (unsigned long long)inserted.load());
+    else std::printf("%d FAILURES\n", g_failures);
+    return g_failures == 0 ? 0 : 1;
+}
+
+// ---- OwnedArrays and HitResult: what a door hands to its caller ------------------------------------------------------------------
+// Under AddressSanitizer an array that is neither committed nor freed is a leak that fails the run at exit, a freed one that
+// is handed out fails at the write below.
+void test_owned_arrays() {
+    for (int commit = 0; commit < 2; ++commit)
+        for (int wanted = 0; wanted < 8; ++wanted) {      // one mandatory array and three optional ones, wanted or not
+            const bool w1 = wanted & 1, w2 = wanted & 2, w3 = wanted & 4;
+            uint32_t* const before32 = reinterpret_cast<uint32_t*>(0x10); double* const before64 = reinterpret_cast<double*>(0x20);
+            uint32_t* o0 = before32; double* o1 = before64; double* o2 = before64; uint32_t* o3 = before32;
+            {
+                OwnedArrays res;
+                uint32_t* a0 = res.add(&o0, 5);
+                double* a1 = res.add(&o1, 3, w1);
+                double* a2 = res.add(w2 ? &o2 : nullptr, 7, w2);      // an optional out parameter that is not there
+                uint32_t* a3 = res.add(&o3, 0, w3);                   // no elements: an array all the same
+                CHECK(res.ok() && a0 && (a1 != nullptr) == w1 && (a2 != nullptr) == w2 && (a3 != nullptr) == w3, "wanted %d: what add() returns", wanted);
+                CHECK(o0 == before32 && o1 == before64 && o2 == before64 && o3 == before32, "wanted %d: add() writes an out parameter", wanted);
+                for (int i = 0; i < 5; ++i) a0[i] = 7;
+                if (a1) a1[2] = 1.5;
+                if (a2) a2[6] = 2.5;
+                if (commit) {
+                    CHECK(res.commit() == YAMS_OK, "commit()");
+                    CHECK(o0 == a0 && o1 == a1 && o3 == a3 && o2 == (w2 ? a2 : before64), "wanted %d: what commit() hands out", wanted);
+                }
+            }
+            if (commit) {      // the caller's now, intact behind the helper's back: freed as the vtable's free function does
+                CHECK(o0[4] == 7 && (!w1 || o1[2] == 1.5) && (!w2 || o2[6] == 2.5), "wanted %d: a committed array changed", wanted);
+                CHECK((o1 != nullptr) == w1 && (o3 != nullptr) == w3, "wanted %d: an unwanted array is handed out", wanted);
+                std::free(o0); std::free(o1); std::free(o3);
+                if (w2) std::free(o2);
+            } else CHECK(o0 == before32 && o1 == before64 && o2 == before64 && o3 == before32, "wanted %d: an uncommitted helper wrote an out parameter", wanted);
+        }
+    {   // an allocation that cannot be had (SIZE_MAX / 2 elements of 8 bytes: beyond size_t): not ok, nothing handed out, and
+        // the arrays that were had go with the helper
+        uint32_t* o0 = nullptr; uint64_t* o1 = reinterpret_cast<uint64_t*>(0x30); float* o2 = nullptr;
+        OwnedArrays res;
+        uint32_t* a0 = res.add(&o0, 16);
+        uint64_t* a1 = res.add(&o1, SIZE_MAX / 2);
+        float* a2 = res.add(&o2, 4);
+        CHECK(!res.ok() && a0 && !a1 && a2, "the impossible allocation");
+        CHECK(o0 == nullptr && o1 == reinterpret_cast<uint64_t*>(0x30) && o2 == nullptr, "a failed helper wrote an out parameter");
+    }
+}
+
+void test_hit_result() {
+    for (uint32_t nq : {0u, 1u, 3u})
+        for (uint32_t k : {0u, 1u, 4u}) {
+            yams_scan_hit_t* hits = nullptr; uint32_t* counts = nullptr;
+            size_t slots;
+            {
+                HitResult res(nq, k);
+                slots = res.slots;
+                CHECK(res.ok() && res.slots == static_cast<size_t>(nq) * (k ? k : 1), "nq %u k %u: %zu slots", nq, k, res.slots);
+                if ((nq + k) % 2) continue;      // not committed: both arrays go with the object
+                CHECK(res.commit(&hits, &counts) == YAMS_OK && hits && counts && !res.hits && !res.counts, "nq %u k %u: commit", nq, k);
+            }
+            for (size_t o = 0; o < slots; ++o)
+                CHECK(hits[o].row == -1 && bits(hits[o].similarity) == 0 && bits(hits[o].distance) == 0, "nq %u k %u: slot %zu is not preset", nq, k, o);
+            for (uint32_t q = 0; q < (nq ? nq : 1); ++q) CHECK(counts[q] == 0, "nq %u k %u: count %u is not zero", nq, k, q);
+            std::free(hits); std::free(counts);
+        }
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "--threads") == 0) return run_threads();
     test_dealing();
     test_mask();
     test_tie_ranks();
@@ -286,6 +444,9 @@ int main() {
     test_pack_hits();
     test_hex_and_chains();
     test_config();
+    test_handle_table();
+    test_owned_arrays();
+    test_hit_result();
     if (g_failures == 0) std::printf("OK (0 failures)\n");
     else std::printf("%d FAILURES\n", g_failures);
     return g_failures == 0 ? 0 : 1;

@@ -18,7 +18,7 @@ LIB = os.path.join(LIBDIR, "libyams_mi355x_accel.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["scan_kernels.hip", "scan_small_kernel.hip", "scan_bf16_kernel.hip", "scan_i8_kernel.hip", "pq_kernels.hip", "doc_kernels.hip", "entity_kernels.hip", "kmeans_kernels.hip", "semgraph_kernels.hip", "sgc_kernels.hip", "artifact_kernels.hip", "route_kernels.hip", "persistence_kernels.hip", "features_kernels.hip", "rerank_kernels.hip", "embed_kernels.hip", "ingest_kernels.hip", "dedup_kernels.hip", "crc32_kernels.hip", "accel_ctx.cpp",
            "scan_api.cpp", "pq_api.cpp", "doc_api.cpp", "entity_api.cpp", "kmeans_api.cpp", "semgraph_api.cpp", "sgc_api.cpp", "artifact_api.cpp", "route_api.cpp", "persistence_api.cpp", "features_api.cpp", "rerank_api.cpp", "embed_api.cpp", "sharded_api.cpp", "dedup_api.cpp",
-           "ingest_api.cpp", "crc32_api.cpp", "plugin.cpp"]
+           "ingest_api.cpp", "crc32_api.cpp", "plugin.cpp", "plugin_topology.cpp", "plugin_content.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-x", "hip"]
 

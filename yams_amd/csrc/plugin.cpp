@@ -1,228 +1,34 @@
 // plugin.cpp — the YAMS plugin surface of libyams_mi355x_accel.so.
 //
-// Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves
-// fifteen interface vtables (vector_scan_v1, vector_doc_scan_v1, vector_entity_scan_v1, topology_cluster_v1,
-// semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1, topology_quality_v1, topology_features_v1, late_interaction_rerank_v1, embedding_pool_v1, content_hash_v1, content_checksum_v1, chunker_v1) written to the
-// conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load
-// this file is AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:
-// 270-442, 657-681): dlopen(RTLD_LAZY|RTLD_LOCAL), yams_plugin_init(config_json, host_context),
-// yams_plugin_get_manifest_json, then yams_plugin_get_interface(id, version, &vtable).
-// What the door computes on the host alone (configuration, row / mask / rank dealing, hit packing, hex) is plugin_host.h.
-#include <algorithm>
-#include <atomic>
-#include <cmath>
-#include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
+// Exports the eight entry points of the reference's include/yams/plugins/abi.h:26-34 and serves fifteen interface vtables
+// written to the conventions of include/yams/plugins/model_provider_v1.h:44-49.  The host side that would load this file is
+// AbiPluginLoader::load / getInterface (src/daemon/resource/abi_plugin_loader.cpp:270-442, 657-681): dlopen(RTLD_LAZY|
+// RTLD_LOCAL), yams_plugin_init(config_json, host_context), yams_plugin_get_manifest_json, then
+// yams_plugin_get_interface(id, version, &vtable).
+//
+// Where the door's parts live:
+//   plugin.cpp            the corpus mirror and the three vtables over it (vector_scan_v1, vector_doc_scan_v1,
+//                         vector_entity_scan_v1), configuration and init, shutdown, health, the table of the fifteen interfaces
+//   plugin_topology.cpp   topology_cluster_v1, semantic_graph_v1, topology_smooth_v1, topology_artifacts_v1, topology_route_v1,
+//                         topology_quality_v1, topology_features_v1, late_interaction_rerank_v1, embedding_pool_v1
+//   plugin_content.cpp    content_hash_v1, content_checksum_v1, chunker_v1
+//   plugin_state.h        what the three share: the guard of every entry, the work-context pool and its lease, the forwarder
+//                         of the entries that only lease and call, the plugin's state
+//   grow_buf.h            the device buffer behind a mirror, which grows in place
+//   plugin_host.h         what the door computes on the host alone (configuration, row / mask / rank dealing, hit packing,
+//                         hex) and its two ownership rules (OwnedArrays / HitResult, HandleTable); tested on the CPU
 #include <chrono>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <shared_mutex>
+#include <cstdio>
 #include <sstream>
-#include <string>
-#include <type_traits>
-#include <vector>
 
-#include "accel_ctx.h"
-#include "plugin_host.h"
+#include "grow_buf.h"
+#include "plugin_state.h"
 
 // The eight entry points and their return codes are declared in include/yams_mi355x_accel.h exactly as
 // the reference's include/yams/plugins/abi.h:18-34 declares them (no local restatement here).
 
-namespace {
-using namespace yams_accel::plugin_host;
-
-// No exception may cross the C ABI (model_provider_v1.h:44-49; the reference's own plugins wrap every entry point,
-// plugins/onnx/model_provider.cpp:51,94,105): every function pointer of the three vtables is the guarded form of
-// its implementation — std::bad_alloc from an absurd batch size, or anything else thrown below, becomes
-// YAMS_ERR_INTERNAL (void functions just return).
-template <auto Fn> struct Guard;
-template <typename R, typename... A, R (*Fn)(A...)> struct Guard<Fn> {
-    static R call(A... a) noexcept {
-        try { return Fn(a...); }
-        catch (...) { if constexpr (!std::is_void_v<R>) return static_cast<R>(YAMS_ERR_INTERNAL); }
-    }
-};
-#define GUARDED(fn) (&Guard<&fn>::call)
-
-// ------------------------------------------------------------------------------------------------
-// A device buffer that grows IN PLACE: one virtual range reserved up front, physical chunks mapped
-// behind it as rows arrive (hipMemAddressReserve / hipMemCreate / hipMemMap / hipMemSetAccess).
-// Appending to a 38 GB mirror maps a few more chunks; nothing is reallocated or copied, pointers
-// handed to running searches stay valid.  (Probed on MI355X: scripts/ubench/vmm_probe.hip.)
-//
-// A virtual address is NEVER reused for a different mapping: scripts/ubench/vmm_stale.hip shows that
-// after hipMemUnmap + a new hipMemMap at the same address, kernels read through stale translations
-// (wrong data in 1-60 % of the trials, even on the stream that did the copy), while re-filling a range
-// that stays mapped is always seen.  So a buffer whose corpus is destroyed is PARKED, mapping intact,
-// and handed to the next corpus on that device (park / unpark below); physical memory goes back to the
-// driver only when the process exits.
-// Parked mappings are adopted BEST-FIT at the next buffer's first ensure() (the smallest one that holds the
-// request; a mapping more than 4x larger than the request is left for a corpus that needs it, a fresh range is
-// reserved instead).  Physical memory goes back to the driver (a) when a device allocation fails while
-// mappings are parked (evict_parked: unmap + RETIRE the range — it stays reserved and is never mapped
-// again, so no stale translation can be hit), and (b) at yams_plugin_shutdown, when no kernel can still be
-// reading through the translations.  Only address space is spent on retired ranges.
-// Falls back to allocate-copy-free growth if the driver refuses the virtual-memory calls.
-// ------------------------------------------------------------------------------------------------
-#ifdef YAMS_ACCEL_MEASURE
-#define GROW_TRACE(what, err) std::fprintf(stderr, "[yams_mi355x_accel] GrowBuf role %d: %s failed (%s); want %zu mapped %zu reserved %zu\n", role, what, hipGetErrorString(err), bytes, mapped, reserved)
-#else
-#define GROW_TRACE(what, err) ((void)0)
-#endif
-struct GrowBuf {
-    int device = 0;
-    int role = 0;               // which array of a shard this is (buffers are parked and reused per role)
-    unsigned char* base = nullptr;
-    size_t reserved = 0, mapped = 0;
-    bool plain = false; // fallback mode: `base` is a hipMalloc allocation of `mapped` bytes
-    std::vector<size_t> chunk_end; // end offset of every physical chunk mapped so far
-
-    static constexpr size_t kGran = 2ull << 20;
-    template <typename T> T* as() const { return reinterpret_cast<T*>(base); }
-
-    // reserve_bytes: the size of the virtual range if this is the buffer's first use (per role: a fixed
-    // fraction of the device's memory, so parked buffers fit every later corpus)
-    bool ensure(size_t bytes, size_t reserve_bytes) {
-        if (bytes <= mapped) return true;
-        (void)hipSetDevice(device);
-        if (!plain && !base) adopt(bytes); // a parked mapping of this (device, role) that fits, if there is one
-        if (bytes <= mapped) return true;
-        if (!plain && !base) {
-            size_t want = std::max(reserve_bytes, bytes);
-            want = (want + kGran - 1) / kGran * kGran;
-            void* va = nullptr;
-            if (hipMemAddressReserve(&va, want, 0, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); plain = true; }
-            else { base = static_cast<unsigned char*>(va); reserved = want; }
-        }
-        if (!plain && bytes > reserved) { GROW_TRACE("beyond reservation", hipSuccess); return false; } // (sized to the device's memory)
-        if (!plain) {
-            // geometric chunks: at least 32 MiB (small side arrays: 2 MiB), at least a quarter of what is mapped
-            size_t add = std::max<size_t>(bytes - mapped, std::max<size_t>(reserved >= (1ull << 30) ? 32ull << 20 : kGran, mapped / 4));
-            add = (add + kGran - 1) / kGran * kGran;
-            if (mapped + add > reserved) add = reserved - mapped;
-            hipMemAllocationProp prop{};
-            prop.type = hipMemAllocationTypePinned;
-            prop.location.type = hipMemLocationTypeDevice;
-            prop.location.id = device;
-            hipMemGenericAllocationHandle_t h;
-            hipError_t e = yams_accel::ya_mem_create(&h, add, &prop);
-            if (e != hipSuccess && evict_parked(device)) { // parked mirrors of destroyed corpora give their memory back first
-                (void)hipGetLastError();
-                if (mapped + (bytes - mapped + kGran - 1) / kGran * kGran <= reserved) add = (bytes - mapped + kGran - 1) / kGran * kGran;
-                e = yams_accel::ya_mem_create(&h, add, &prop);
-            }
-            if (e != hipSuccess) { GROW_TRACE("hipMemCreate", e); (void)hipGetLastError(); return false; }
-            hipMemAccessDesc acc{};
-            acc.location = prop.location;
-            acc.flags = hipMemAccessFlagsProtReadWrite;
-            e = hipMemMap(base + mapped, add, 0, h, 0);
-            // access is set over the WHOLE mapped range: on a sub-range that starts at a later chunk the call
-            // returns "invalid argument" as soon as chunk sizes differ (scripts/ubench/vmm_map.hip)
-            const bool was_mapped = e == hipSuccess;
-            if (e == hipSuccess) e = hipMemSetAccess(base, mapped + add, &acc, 1);
-            if (e != hipSuccess && was_mapped) (void)hipMemUnmap(base + mapped, add); // never touched: safe to unmap
-            if (e != hipSuccess) { GROW_TRACE("hipMemMap/SetAccess", e); (void)hipGetLastError(); (void)hipMemRelease(h); return false; }
-            (void)hipMemRelease(h); // the mapping keeps the memory alive; it is never unmapped (see above)
-            mapped += add;
-            chunk_end.push_back(mapped);
-            return true;
-        }
-        // fallback: allocate, copy, free
-        const size_t want = std::max(bytes, mapped + mapped / 2);
-        void* nd = nullptr;
-        if (yams_accel::ya_malloc(&nd, want) != hipSuccess) { (void)hipGetLastError(); return false; }
-        if (mapped && hipMemcpy(nd, base, mapped, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(nd); return false; }
-        if (base) (void)hipFree(base);
-        base = static_cast<unsigned char*>(nd);
-        mapped = want;
-        return true;
-    }
-    // Host -> device copy into [off, off+bytes).  The runtime's copy wants its destination inside ONE
-    // allocation, so a range that crosses physical chunks goes as one copy per chunk.
-    bool h2d(size_t off, const void* src, size_t bytes, hipStream_t stream) const {
-        if (off + bytes > mapped) return false;
-        const unsigned char* sp = static_cast<const unsigned char*>(src);
-        size_t ci = 0;
-        while (bytes) {
-            size_t end = off + bytes;
-            if (!plain) {
-                while (ci < chunk_end.size() && chunk_end[ci] <= off) ++ci;
-                if (ci < chunk_end.size()) end = std::min(end, chunk_end[ci]);
-            }
-            if (yams_accel::staged_h2d(base + off, sp, end - off, stream) != hipSuccess) { (void)hipGetLastError(); return false; } // (pinned ring: link rate from pageable memory)
-            sp += end - off; bytes -= end - off; off = end;
-        }
-        return true;
-    }
-    void release();            // parks the mapping for the next corpus (or frees a fallback allocation)
-    void adopt(size_t bytes);  // takes the best-fitting parked mapping of the same (device, role), if there is one
-    void unmap_and_retire();   // gives the physical memory back; the virtual range stays reserved, never mapped again
-    static bool evict_parked(int device);   // all parked mappings of a device; true if anything was freed
-    static void evict_all_parked();
-};
-
-// parked mappings, per (device, role), until a corpus adopts them, memory runs short or the plugin shuts down
-std::mutex g_park_mu;
-std::map<std::pair<int, int>, std::vector<GrowBuf>> g_parked;
-
-void GrowBuf::release() {
-    if (plain) { (void)hipSetDevice(device); if (base) (void)hipFree(base); }
-    else if (base) {
-        std::lock_guard<std::mutex> lk(g_park_mu);
-        g_parked[{device, role}].push_back(*this);
-    }
-    base = nullptr; reserved = mapped = 0; plain = false; chunk_end.clear();
-}
-void GrowBuf::adopt(size_t bytes) {
-    if (base) return;
-    std::lock_guard<std::mutex> lk(g_park_mu);
-    auto& v = g_parked[{device, role}];
-    if (v.empty()) return;
-    // best fit: the smallest parked mapping that holds the request — but not one more than 4x larger (a small
-    // corpus must not pin the mirror of a destroyed 100 GB one; that one waits for a corpus of its size).
-    // Nothing large enough: the largest one that is not larger than needed, it grows in place.
-    size_t best = v.size();
-    for (size_t i = 0; i < v.size(); ++i)
-        if (v[i].mapped >= bytes && v[i].mapped / 4 <= std::max<size_t>(bytes, 64ull << 20) && (best == v.size() || v[i].mapped < v[best].mapped)) best = i;
-    if (best == v.size())
-        for (size_t i = 0; i < v.size(); ++i)
-            if (v[i].mapped < bytes && v[i].reserved >= bytes && (best == v.size() || v[i].mapped > v[best].mapped)) best = i;
-    if (best == v.size()) return;
-    base = v[best].base; reserved = v[best].reserved; mapped = v[best].mapped; chunk_end = std::move(v[best].chunk_end);
-    v.erase(v.begin() + static_cast<std::ptrdiff_t>(best));
-}
-void GrowBuf::unmap_and_retire() {
-    if (plain || !base) return;
-    (void)hipSetDevice(device);
-    (void)hipDeviceSynchronize(); // nothing may still read through these translations
-    size_t off = 0;
-    for (size_t end : chunk_end) { if (hipMemUnmap(base + off, end - off) != hipSuccess) (void)hipGetLastError(); off = end; }
-    // the range itself is NOT freed: a later reservation could land on it, and a mapping at an address that
-    // was mapped before is read through stale translations on this driver (scripts/ubench/vmm_stale.hip)
-    base = nullptr; reserved = mapped = 0; chunk_end.clear();
-}
-bool GrowBuf::evict_parked(int device) {
-    std::vector<GrowBuf> victims;
-    {
-        std::lock_guard<std::mutex> lk(g_park_mu);
-        for (auto& kv : g_parked)
-            if (kv.first.first == device) { for (auto& b : kv.second) victims.push_back(std::move(b)); kv.second.clear(); }
-    }
-    size_t freed = 0;
-    for (auto& b : victims) { freed += b.mapped; b.unmap_and_retire(); }
-    return freed != 0;
-}
-void GrowBuf::evict_all_parked() {
-    std::vector<int> devs;
-    {
-        std::lock_guard<std::mutex> lk(g_park_mu);
-        for (auto& kv : g_parked) if (!kv.second.empty()) devs.push_back(kv.first.first);
-    }
-    for (int d : devs) (void)evict_parked(d);
-}
+namespace yams_accel {
+namespace door {
 
 // One shard of a corpus: the rows dealt to one device, plus their filter shadows.
 struct ShardStore {
@@ -298,63 +104,14 @@ struct Corpus {
     std::shared_mutex mu;            // searches share, mutations exclude (vector_database.cpp:539,618)
 };
 
+PluginState& g = *new PluginState;   // never destroyed: when a host exits without yams_plugin_shutdown, the corpora's DevArrays must
+                                     // not reach hipFree from a static destructor (the runtime may have gone before them)
+
+namespace {
+
 // rows of a stripe when a corpus is dealt to several devices (config "stripe_rows", a multiple of 64;
 // fixed at init: it is part of every corpus's row -> shard map)
 uint32_t kStripeRows = 65536;
-
-// A pool of N identical resources handed out to concurrent calls.
-template <typename T> class Pool {
-public:
-    void add(T v) { std::lock_guard<std::mutex> lk(mu_); free_.push_back(v); all_.push_back(v); }
-    T acquire() {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return !free_.empty(); });
-        T v = free_.back(); free_.pop_back();
-        return v;
-    }
-    void release(T v) { { std::lock_guard<std::mutex> lk(mu_); free_.push_back(v); } cv_.notify_one(); }
-    std::vector<T> drain() { std::lock_guard<std::mutex> lk(mu_); auto a = all_; all_.clear(); free_.clear(); return a; }
-    size_t size() const { return all_.size(); }
-private:
-    std::mutex mu_;
-    std::condition_variable cv_;
-    std::vector<T> free_, all_;
-};
-template <typename T> struct Lease {
-    Pool<T>& pool; T v;
-    explicit Lease(Pool<T>& p) : pool(p), v(p.acquire()) {}
-    ~Lease() { pool.release(v); }
-};
-
-struct PluginState {
-    std::shared_mutex mu;            // init / shutdown exclude everything else; calls share
-    bool initialised = false;
-    std::vector<int> devices;        // config "devices": [..] (or "device": n); rows are striped over them
-    bool want_bf16 = true, want_i8 = true;
-    int i8_layout = 0;               // configuration "i8_layout": 0 auto (measured at a corpus' first append), 1 plain, 2 rotated
-    std::string init_error;
-    // searches: ONE sharded handle over the plugin's devices (one RCCL communicator when there are several),
-    // "search_slots" lanes = concurrent searches in flight, each on its own contexts / streams / worker threads;
-    // the lanes of one device share a sweep gate inside the handle (sharded_api.cpp)
-    yams_scan_sharded* sharded = nullptr;
-    uint32_t search_slots = 0;
-    uint32_t l2_acc = YAMS_SCAN_FLAG_L2_ACC_F64;   // config "l2_accumulate": "f64" | "f32" | "f32x8" | "f32x16"
-    // the last corpus_append: bytes, ms spent mapping device memory / copying / building shadows (written under upload_mu,
-    // read by the health call without it: atomics), and the slowest append so far with its split
-    std::atomic<uint64_t> append_bytes{0}, appends{0};
-    std::atomic<double> append_map_ms{0}, append_copy_ms{0}, append_shadow_ms{0};
-    std::atomic<double> slow_append_ms{0}, slow_map_ms{0}, slow_copy_ms{0}, slow_shadow_ms{0};
-    std::atomic<uint64_t> slow_append_bytes{0}, exhausted_appends{0};
-    Pool<yams_accel_ctx*> work_ctx;          // hashing / chunking contexts on devices[0]
-    std::vector<yams_accel_ctx*> upload_ctx; // one per device, used under a corpus's exclusive lock
-    std::mutex upload_mu;                    // (upload contexts are shared by all corpora)
-    std::mutex corpora_mu;
-    std::map<uint64_t, std::shared_ptr<Corpus>> corpora;
-    uint64_t next_id = 1;
-    std::atomic<uint64_t> searches{0}, hashes{0}, chunk_calls{0}, refused_chains{0}, deferred_chains{0};
-};
-PluginState& g = *new PluginState;   // never destroyed: when a host exits without yams_plugin_shutdown, the corpora's DevArrays must
-                                     // not reach hipFree from a static destructor (the runtime may have gone before them)
 
 const char kManifest[] =
     "{\"name\":\"yams_mi355x_accel\",\"version\":\"" YAMS_ACCEL_VERSION_STRING "\",\"abi\":1,"
@@ -362,13 +119,7 @@ const char kManifest[] =
     "\"interfaces\":[{\"id\":\"vector_scan_v1\",\"version\":1},"
     "{\"id\":\"content_hash_v1\",\"version\":1},{\"id\":\"chunker_v1\",\"version\":3}]}";
 
-std::shared_ptr<Corpus> find_corpus(uint64_t id) {
-    std::lock_guard<std::mutex> lk(g.corpora_mu);
-    auto it = g.corpora.find(id);
-    return it == g.corpora.end() ? nullptr : it->second;
-}
-
-#define NEED_INIT() std::shared_lock<std::shared_mutex> init_lk__(g.mu); do { if (!g.initialised) return YAMS_ERR_UNSUPPORTED; } while (0)
+std::shared_ptr<Corpus> find_corpus(uint64_t id) { return g.corpora.find(id); }
 
 // Which filter shadows a corpus of this dimension has: vs_corpus_append builds exactly these and view_of hands out exactly
 // these (a view naming a shadow that was never built would have the int8 tier's proof accept wrong rows in silence).
@@ -388,28 +139,6 @@ yams_scan_corpus_t view_of(const Corpus& c, uint32_t i, unsigned what) {
     if ((what & kViewStripes) && c.sh.size() > 1) { v.stripe_rows = kStripeRows; v.n_stripes = static_cast<uint32_t>(c.sh.size()); v.stripe_index = i; }
     return v;
 }
-
-// The malloc'd result of a search: hits[nq * max(k, 1)], every row preset to -1, and counts[max(nq, 1)], zeroed.  commit()
-// hands both to the caller (who frees them through the vtable's free function); what was not committed goes with the object.
-struct HitResult {
-    const size_t slots;
-    uint32_t* counts;
-    yams_scan_hit_t* hits;
-    HitResult(uint32_t nq, uint32_t k)
-        : slots(static_cast<size_t>(nq) * std::max<uint32_t>(k, 1)),
-          counts(static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)))),
-          hits(static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)))) {
-        for (size_t o = 0; hits && o < slots; ++o) hits[o].row = -1;
-    }
-    HitResult(const HitResult&) = delete;
-    ~HitResult() { std::free(counts); std::free(hits); }
-    bool ok() const { return counts && hits; }
-    yams_status_t commit(yams_scan_hit_t** out_hits, uint32_t** out_counts) {
-        *out_hits = hits; *out_counts = counts;
-        hits = nullptr; counts = nullptr;
-        return YAMS_OK;
-    }
-};
 
 // The host's allow-mask (document_hash / candidate_hashes restriction, :4137-4175; tombstones), dealt like the rows: shard i's
 // part goes into workspace `name` of the context (its device is current) and into the shard's view.
@@ -437,9 +166,7 @@ yams_status_t vs_corpus_create(void*, uint32_t dim, uint64_t* out_id) {
         for (GrowBuf* b : {&s.rows, &s.bf16, &s.i8, &s.nsq, &s.i8meta, &s.tie, &s.inv}) { b->device = s.device; b->role = role++; }
     }
     c->rank_of_row.device = g.devices[0]; c->rank_of_row.role = 7; // (parked mappings are adopted at the first ensure(), best fit)
-    std::lock_guard<std::mutex> lk(g.corpora_mu);
-    *out_id = g.next_id++;
-    g.corpora[*out_id] = c;
+    *out_id = g.corpora.insert(c);
     return YAMS_OK;
 }
 
@@ -623,14 +350,8 @@ yams_status_t vs_corpus_clear(void*, uint64_t id) {
 
 yams_status_t vs_corpus_destroy(void*, uint64_t id) {
     NEED_INIT();
-    std::shared_ptr<Corpus> c;
-    {
-        std::lock_guard<std::mutex> lk(g.corpora_mu);
-        auto it = g.corpora.find(id);
-        if (it == g.corpora.end()) return YAMS_ERR_NOT_FOUND;
-        c = it->second;
-        g.corpora.erase(it);
-    }
+    auto c = g.corpora.take(id);
+    if (!c) return YAMS_ERR_NOT_FOUND;
     std::unique_lock<std::shared_mutex> lk(c->mu);
     release_corpus(*c);
     return YAMS_OK;
@@ -821,19 +542,12 @@ yams_status_t vs_search_pq(void*, uint64_t id, const float* queries, const float
         });
 }
 
-void vs_free_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::free(hits); std::free(counts); }
 
-yams_status_t vs_runtime_info(void*, char** out_json) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    return yams_accel_device_info_json(w.v, out_json);
-}
-void vs_free_string(void*, char* s) { std::free(s); }
 
 yams_vector_scan_v1 g_vector_scan = {
     YAMS_IFACE_VECTOR_SCAN_V1_VERSION, nullptr, GUARDED(vs_corpus_create), GUARDED(vs_corpus_append),
     GUARDED(vs_corpus_set_tie_ranks), GUARDED(vs_corpus_clear), GUARDED(vs_corpus_destroy), GUARDED(vs_corpus_size),
-    GUARDED(vs_search_batch), GUARDED(vs_free_hits), GUARDED(vs_runtime_info), GUARDED(vs_free_string),
+    GUARDED(vs_search_batch), GUARDED(free_arrays<yams_scan_hit_t, uint32_t>), GUARDED(Leased<&yams_accel_device_info_json>::call), GUARDED(free_arrays<char>),
     GUARDED(vs_search_batch_masked), GUARDED(vs_search_batch_ex), GUARDED(vs_pq_index_set), GUARDED(vs_search_pq)};
 
 // ---- vector_doc_scan_v1: document-level selection over a vector_scan_v1 corpus (yams_scan_doc_topk_device) -----------------
@@ -883,10 +597,8 @@ yams_status_t ds_search_docs(void*, uint64_t id, const float* queries, uint32_t 
         });
 }
 
-void ds_free_doc_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::free(hits); std::free(counts); }
-
 yams_vector_doc_scan_v1 g_vector_doc_scan = {YAMS_IFACE_VECTOR_DOC_SCAN_V1_VERSION, nullptr, GUARDED(ds_corpus_set_documents),
-                                             GUARDED(ds_search_docs), GUARDED(ds_free_doc_hits)};
+                                             GUARDED(ds_search_docs), GUARDED(free_arrays<yams_scan_hit_t, uint32_t>)};
 
 // ---- vector_entity_scan_v1: IEntityStore::searchEntities over a vector_scan_v1 corpus (yams_scan_entity_topk_device) ---------
 yams_status_t es_corpus_set_attributes(void*, uint64_t id, uint64_t first_row, uint64_t n_rows, const uint8_t* types,
@@ -947,778 +659,13 @@ yams_status_t es_search_entities(void*, uint64_t id, const float* queries, const
         });
 }
 
-void es_free_entity_hits(void*, yams_scan_hit_t* hits, uint32_t* counts) { std::free(hits); std::free(counts); }
-
 yams_vector_entity_scan_v1 g_vector_entity_scan = {YAMS_IFACE_VECTOR_ENTITY_SCAN_V1_VERSION, nullptr, GUARDED(es_corpus_set_attributes),
-                                                   GUARDED(es_search_entities), GUARDED(es_free_entity_hits)};
-
-// ---- topology_cluster_v1: the topology build's k-means over host memory (yams_cluster_kmeans_host / _assign_device) --------
-yams_status_t tc_kmeans(void*, const float* rows, uint64_t n, uint32_t dim, uint32_t k, uint32_t max_iterations,
-                        uint32_t** out_membership, float** out_centroids, uint32_t* out_k, uint32_t* out_iterations) {
-    NEED_INIT();
-    if (!out_membership) return YAMS_ERR_INVALID_ARG;
-    *out_membership = nullptr;
-    if (out_centroids) *out_centroids = nullptr;
-    if (out_k) *out_k = 0;
-    if (out_iterations) *out_iterations = 0;
-    if (n == 0) return YAMS_OK;
-    if (dim == 0 || !rows || n < 2) return YAMS_ERR_INVALID_ARG;
-    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM) return YAMS_ERR_UNSUPPORTED;
-    // the clamped k bounds the centroid array (:367-371)
-    uint64_t kk = k ? k : static_cast<uint64_t>(std::round(std::sqrt(static_cast<double>(n))));
-    kk = std::min<uint64_t>(std::max<uint64_t>(kk, 2), n);
-    if (kk > YAMS_CLUSTER_MAX_K) return YAMS_ERR_UNSUPPORTED;
-    auto* mem = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n) * 4));
-    auto* cent = out_centroids ? static_cast<float*>(std::malloc(static_cast<size_t>(kk) * dim * 4)) : nullptr;
-    if (!mem || (out_centroids && !cent)) { std::free(mem); std::free(cent); return YAMS_ERR_RESOURCE_EXHAUSTED; }
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    const yams_status_t st = yams_cluster_kmeans_host(w.v, rows, n, dim, k, max_iterations, mem, cent, out_k, out_iterations);
-    if (st != YAMS_OK) { std::free(mem); std::free(cent); return st; }
-    *out_membership = mem;
-    if (out_centroids) *out_centroids = cent;
-    return YAMS_OK;
-}
-
-yams_status_t tc_assign(void*, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_centroids,
-                        const uint8_t* centroid_empty, uint32_t** out_assign, double** out_distance) {
-    NEED_INIT();
-    if (!out_assign) return YAMS_ERR_INVALID_ARG;
-    *out_assign = nullptr;
-    if (out_distance) *out_distance = nullptr;
-    if (n == 0) return YAMS_OK;
-    if (dim == 0 || !rows || (n_centroids && !centroids)) return YAMS_ERR_INVALID_ARG;
-    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM || n_centroids > YAMS_CLUSTER_MAX_K) return YAMS_ERR_UNSUPPORTED;
-    auto* asg = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n) * 4));
-    auto* dist = out_distance ? static_cast<double*>(std::malloc(static_cast<size_t>(n) * 8)) : nullptr;
-    if (!asg || (out_distance && !dist)) { std::free(asg); std::free(dist); return YAMS_ERR_RESOURCE_EXHAUSTED; }
-    auto done = [&](yams_status_t st) { if (st != YAMS_OK) { std::free(asg); std::free(dist); } else { *out_assign = asg; if (out_distance) *out_distance = dist; } return st; };
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    yams_accel_ctx* x = w.v;
-    const size_t rb = static_cast<size_t>(n) * dim * 4, cb = static_cast<size_t>(n_centroids) * dim * 4;
-    float* d_rows; float* d_cent; uint8_t* d_empty = nullptr; uint32_t* d_asg; double* d_dist = nullptr;
-    yams_status_t st;
-    if ((st = yams_accel::ws_get(x, "plugin_tc_rows", rb, (void**)&d_rows)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_tc_centroids", cb + 16, (void**)&d_cent)) != YAMS_OK) return done(st);
-    if ((st = yams_accel::ws_get(x, "plugin_tc_assign", static_cast<size_t>(n) * 4, (void**)&d_asg)) != YAMS_OK) return done(st);
-    if (out_distance && (st = yams_accel::ws_get(x, "plugin_tc_distance", static_cast<size_t>(n) * 8, (void**)&d_dist)) != YAMS_OK) return done(st);
-    if (centroid_empty && n_centroids) {
-        if ((st = yams_accel::ws_get(x, "plugin_tc_empty", n_centroids, (void**)&d_empty)) != YAMS_OK) return done(st);
-        if (yams_accel_upload(x, d_empty, centroid_empty, n_centroids) != YAMS_OK) return done(YAMS_ERR_INTERNAL);
-    }
-    if (yams_accel_upload(x, d_rows, rows, rb) != YAMS_OK || (cb && yams_accel_upload(x, d_cent, centroids, cb) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
-    if ((st = yams_cluster_assign_device(x, d_rows, n, dim, d_cent, n_centroids, d_empty, d_asg, d_dist)) != YAMS_OK) return done(st);
-    if (yams_accel_download(x, asg, d_asg, static_cast<size_t>(n) * 4) != YAMS_OK ||
-        (dist && yams_accel_download(x, dist, d_dist, static_cast<size_t>(n) * 8) != YAMS_OK)) return done(YAMS_ERR_INTERNAL);
-    return done(YAMS_OK);
-}
-
-void tc_free_clusters(void*, uint32_t* membership, float* centroids) { std::free(membership); std::free(centroids); }
-void tc_free_assignment(void*, uint32_t* assign, double* distance) { std::free(assign); std::free(distance); }
-
-yams_topology_cluster_v1 g_topology_cluster = {YAMS_IFACE_TOPOLOGY_CLUSTER_V1_VERSION, nullptr, GUARDED(tc_kmeans), GUARDED(tc_assign),
-                                               GUARDED(tc_free_clusters), GUARDED(tc_free_assignment)};
-
-// ---- semantic_graph_v1: the semantic-neighbour graph over host memory (yams_graph_semantic_neighbors_host) ------------------
-yams_status_t sg_neighbors(void*, const float* rows, uint64_t n, uint32_t dim, const uint32_t* tie_rank, const uint32_t* source_rows,
-                           uint64_t n_sources, uint32_t k, uint32_t flags, float threshold, uint32_t** out_rows, float** out_sims,
-                           uint32_t** out_counts, float** out_inv_norm, yams_graph_diag_t* out_diag) {
-    NEED_INIT();
-    if (!out_rows || !out_sims || !out_counts) return YAMS_ERR_INVALID_ARG;
-    *out_rows = nullptr; *out_sims = nullptr; *out_counts = nullptr;
-    if (out_inv_norm) *out_inv_norm = nullptr;
-    if (out_diag) std::memset(out_diag, 0, sizeof *out_diag);
-    const uint64_t S = source_rows ? n_sources : n;
-    // the limits bound the arrays allocated here; every other check is the flat entry's
-    if (n >= (1ull << 31) || S >= (1ull << 31) || dim > YAMS_GRAPH_MAX_DIM || k > YAMS_GRAPH_MAX_K) return YAMS_ERR_UNSUPPORTED;
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    if (k == 0 || n < 2 || S == 0)      // an empty result: null arrays (the flat entry still judges flags and threshold)
-        return yams_graph_semantic_neighbors_host(w.v, rows, n, dim, tie_rank, source_rows, n_sources, k, flags, threshold, nullptr, nullptr,
-                                                  nullptr, nullptr, out_diag);
-    const size_t slots = static_cast<size_t>(S) * k;
-    auto* r = static_cast<uint32_t*>(std::malloc(slots * 4));
-    auto* s = static_cast<float*>(std::malloc(slots * 4));
-    auto* c = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(S) * 4));
-    auto* iv = out_inv_norm ? static_cast<float*>(std::malloc(static_cast<size_t>(n) * 4)) : nullptr;
-    auto drop = [&] { std::free(r); std::free(s); std::free(c); std::free(iv); };
-    if (!r || !s || !c || (out_inv_norm && !iv)) { drop(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
-    const yams_status_t st = yams_graph_semantic_neighbors_host(w.v, rows, n, dim, tie_rank, source_rows, n_sources, k, flags, threshold, r, s, c,
-                                                                iv, out_diag);
-    if (st != YAMS_OK) { drop(); return st; }
-    *out_rows = r; *out_sims = s; *out_counts = c;
-    if (out_inv_norm) *out_inv_norm = iv;
-    return YAMS_OK;
-}
-
-void sg_free_neighbors(void*, uint32_t* rows, float* sims, uint32_t* counts, float* inv_norm) {
-    std::free(rows); std::free(sims); std::free(counts); std::free(inv_norm);
-}
-
-yams_semantic_graph_v1 g_semantic_graph = {YAMS_IFACE_SEMANTIC_GRAPH_V1_VERSION, nullptr, GUARDED(sg_neighbors), GUARDED(sg_free_neighbors)};
-
-// ---- topology_smooth_v1: SGC smoothing over host memory (yams_graph_sgc_smooth_host) -----------------------------------------
-yams_status_t ts_smooth(void*, const float* rows, uint64_t n, uint32_t dim, const uint64_t* row_offsets, const uint32_t* cols,
-                        const float* weights, uint32_t hops, float* out, yams_sgc_diag_t* out_diag) {
-    NEED_INIT();
-    if (out_diag) std::memset(out_diag, 0, sizeof *out_diag);
-    Lease<yams_accel_ctx*> w(g.work_ctx);      // every check is the flat entry's: the caller owns every array
-    return yams_graph_sgc_smooth_host(w.v, rows, n, dim, row_offsets, cols, weights, hops, out, out_diag);
-}
-
-yams_topology_smooth_v1 g_topology_smooth = {YAMS_IFACE_TOPOLOGY_SMOOTH_V1_VERSION, nullptr, GUARDED(ts_smooth)};
-
-// ---- topology_artifacts_v1: centroids, representatives, residuals over host memory (yams_cluster_*_host) -------------------
-// the limits bound the arrays allocated here; every other check is the flat entries'
-yams_status_t ta_centroids(void*, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets, const uint32_t* members,
-                           uint32_t n_clusters, float** out_centroids, uint32_t** out_counts) {
-    NEED_INIT();
-    if (!out_centroids || !out_counts) return YAMS_ERR_INVALID_ARG;
-    *out_centroids = nullptr; *out_counts = nullptr;
-    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM || n_clusters > YAMS_CLUSTER_MAX_K) return YAMS_ERR_UNSUPPORTED;
-    if (dim == 0) return YAMS_ERR_INVALID_ARG;
-    if (n_clusters == 0) return YAMS_OK;
-    auto* cent = static_cast<float*>(std::malloc(static_cast<size_t>(n_clusters) * dim * 4));
-    auto* cnt = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n_clusters) * 4));
-    if (!cent || !cnt) { std::free(cent); std::free(cnt); return YAMS_ERR_RESOURCE_EXHAUSTED; }
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    const yams_status_t st = yams_cluster_centroids_host(w.v, rows, n, dim, cluster_offsets, members, n_clusters, cent, cnt);
-    if (st != YAMS_OK) { std::free(cent); std::free(cnt); return st; }
-    *out_centroids = cent; *out_counts = cnt;
-    return YAMS_OK;
-}
-
-yams_status_t ta_representatives(void*, const float* rows, uint64_t n, uint32_t dim, const uint64_t* cluster_offsets,
-                                 const uint32_t* candidates, const float* centroids, const uint8_t* centroid_empty, uint32_t n_clusters,
-                                 uint32_t n_extra, uint32_t** out_selected, uint32_t** out_counts) {
-    NEED_INIT();
-    if (!out_selected || !out_counts) return YAMS_ERR_INVALID_ARG;
-    *out_selected = nullptr; *out_counts = nullptr;
-    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM || n_clusters > YAMS_CLUSTER_MAX_K || n_extra > YAMS_CLUSTER_MAX_REPRESENTATIVES)
-        return YAMS_ERR_UNSUPPORTED;
-    if (dim == 0) return YAMS_ERR_INVALID_ARG;
-    if (n_clusters == 0) return YAMS_OK;
-    auto* sel = n_extra ? static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n_clusters) * n_extra * 4)) : nullptr;
-    auto* cnt = static_cast<uint32_t*>(std::malloc(static_cast<size_t>(n_clusters) * 4));
-    if ((n_extra && !sel) || !cnt) { std::free(sel); std::free(cnt); return YAMS_ERR_RESOURCE_EXHAUSTED; }
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    const yams_status_t st = yams_cluster_representatives_host(w.v, rows, n, dim, cluster_offsets, candidates, centroids, centroid_empty,
-                                                               n_clusters, n_extra, sel, cnt);
-    if (st != YAMS_OK) { std::free(sel); std::free(cnt); return st; }
-    *out_selected = sel; *out_counts = cnt;
-    return YAMS_OK;
-}
-
-yams_status_t ta_residuals(void*, const float* rows, uint64_t n, uint32_t dim, const float* centroids, uint32_t n_clusters,
-                           const uint32_t* primary, const uint64_t* cand_offsets, const uint32_t* cand, uint32_t form,
-                           double** out_primary_norm_sq, double** out_cand_norm_sq, double** out_residual_dot) {
-    NEED_INIT();
-    if (!out_cand_norm_sq || (primary && (!out_primary_norm_sq || !out_residual_dot))) return YAMS_ERR_INVALID_ARG;
-    *out_cand_norm_sq = nullptr;
-    if (out_primary_norm_sq) *out_primary_norm_sq = nullptr;
-    if (out_residual_dot) *out_residual_dot = nullptr;
-    if (n >= (1ull << 31) || dim > YAMS_CLUSTER_MAX_DIM || n_clusters > YAMS_CLUSTER_MAX_K) return YAMS_ERR_UNSUPPORTED;
-    if (dim == 0 || (cand_offsets == nullptr) != (cand == nullptr)) return YAMS_ERR_INVALID_ARG;
-    if (n == 0) return YAMS_OK;
-    if (cand_offsets)      // the offsets size the arrays: judged here first
-        for (uint64_t i = 0; i < n; ++i)
-            if (cand_offsets[0] != 0 || cand_offsets[i + 1] < cand_offsets[i]) return YAMS_ERR_INVALID_ARG;
-    const uint64_t pairs = cand_offsets ? cand_offsets[n] : n * n_clusters;
-    const size_t p1 = static_cast<size_t>(pairs ? pairs : 1);
-    auto* cn = static_cast<double*>(std::malloc(p1 * 8));
-    auto* pn = primary ? static_cast<double*>(std::malloc(static_cast<size_t>(n) * 8)) : nullptr;
-    auto* rd = primary ? static_cast<double*>(std::malloc(p1 * 8)) : nullptr;
-    auto drop = [&] { std::free(cn); std::free(pn); std::free(rd); };
-    if (!cn || (primary && (!pn || !rd))) { drop(); return YAMS_ERR_RESOURCE_EXHAUSTED; }
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    const yams_status_t st = yams_cluster_residuals_host(w.v, rows, n, dim, centroids, n_clusters, primary, cand_offsets, cand, form, pn, cn, rd);
-    if (st != YAMS_OK) { drop(); return st; }
-    *out_cand_norm_sq = cn;
-    if (primary) { *out_primary_norm_sq = pn; *out_residual_dot = rd; }
-    return YAMS_OK;
-}
-
-void ta_free_centroids(void*, float* centroids, uint32_t* counts) { std::free(centroids); std::free(counts); }
-void ta_free_representatives(void*, uint32_t* selected, uint32_t* counts) { std::free(selected); std::free(counts); }
-void ta_free_residuals(void*, double* primary_norm_sq, double* cand_norm_sq, double* residual_dot) {
-    std::free(primary_norm_sq); std::free(cand_norm_sq); std::free(residual_dot);
-}
-
-yams_topology_artifacts_v1 g_topology_artifacts = {YAMS_IFACE_TOPOLOGY_ARTIFACTS_V1_VERSION, nullptr, GUARDED(ta_centroids),
-                                                   GUARDED(ta_representatives), GUARDED(ta_residuals), GUARDED(ta_free_centroids),
-                                                   GUARDED(ta_free_representatives), GUARDED(ta_free_residuals)};
-
-// ---- content_hash_v1 --------------------------------------------------------------------------
-// Every call leases one of the plugin's work contexts (own stream, own workspace), so hashing, chunking
-// and searches of different host threads overlap on the device instead of queueing on one mutex.
-// One SHA-256 chain is sequential: ~35 MB/s on a device lane, > 1 GB/s on a host core.  Work the device is worse
-// at is refused (YAMS_ERR_UNSUPPORTED: the host hashes it itself), not served slowly — see the header.
-yams_status_t ch_hash(void*, const uint8_t* data, size_t n, char out_hex[65]) {
-    NEED_INIT();
-    if (n > YAMS_HASH_LONE_CHAIN_MAX) { ++g.refused_chains; return YAMS_ERR_UNSUPPORTED; }
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    ++g.hashes;
-    return yams_sha256_host(w.v, data, n, out_hex);
-}
-yams_status_t ch_hash_many(void*, const uint8_t* const* msgs, const size_t* lens, size_t n, char* out_hex) {
-    NEED_INIT();
-    if (n && lens && !chains_suit_the_device(lens, n)) { ++g.refused_chains; return YAMS_ERR_UNSUPPORTED; }
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    g.hashes += n;
-    return yams_sha256_many_host(w.v, msgs, lens, n, out_hex);
-}
-
-// Streaming state (sha256_hasher.cpp:81-109).  update() only BUFFERS on the host: one SHA-256 chain is
-// sequential, a launch + sync per update would cost more than the hashing.  Whole 64-byte blocks are
-// pushed through the device in pieces of kStreamFlush bytes (one upload + one kernel each), the tail
-// and the FIPS 180-4 padding at finalize().  A handle is a single-threaded object, like the reference's
-// hasher (sha256_hasher.cpp:34).
-struct HashStream {
-    uint32_t state[8];
-    std::vector<uint8_t> pending; // bytes not yet compressed
-    uint64_t total = 0;           // bytes compressed so far + pending
-};
-constexpr size_t kStreamFlush = 64u << 20;
-const uint32_t kShaInit[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
-                              0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-}  // namespace
-
-namespace yams_accel { // from ingest_kernels.hip
-hipError_t launch_sha256(hipStream_t st, const uint8_t* data, const uint64_t* offs,
-                         const uint64_t* lens, uint64_t n_long, uint64_t n_msgs, uint8_t* digests,
-                         unsigned long long* queue_heads, const uint32_t* init_state,
-                         uint32_t* out_state, int raw_blocks_only, uint32_t max_blocks, int slots);
-}
-
-namespace {
-// Runs the compression function over `n` bytes (a multiple of 64) starting from hs->state.
-yams_status_t stream_blocks(yams_accel_ctx* ctx, HashStream* hs, const uint8_t* bytes, size_t n) {
-    using namespace yams_accel;
-    if (n == 0) return YAMS_OK;
-    (void)hipSetDevice(ctx->device);
-    uint8_t* d_data; uint64_t* d_tab; uint32_t* d_state; unsigned long long* d_head;
-    YA_TRY(ws_get(ctx, "hs_data", n + 64, (void**)&d_data));
-    YA_TRY(ws_get(ctx, "hs_tab", 64, (void**)&d_tab));
-    YA_TRY(ws_get(ctx, "hs_state", 64, (void**)&d_state));
-    YA_TRY(ws_get(ctx, "ing_queue", 64, (void**)&d_head));
-    const uint64_t tab[2] = {0, n};
-    uint32_t out[8];
-    YA_HIP(ctx, hipMemcpyAsync(d_data, bytes, n, hipMemcpyHostToDevice, ctx->stream));
-    YA_HIP(ctx, hipMemcpyAsync(d_tab, tab, 16, hipMemcpyHostToDevice, ctx->stream));
-    YA_HIP(ctx, hipMemcpyAsync(d_state, hs->state, 32, hipMemcpyHostToDevice, ctx->stream));
-    YA_HIP(ctx, launch_sha256(ctx->stream, d_data, d_tab, d_tab + 1, 0, 1, nullptr, d_head, d_state,
-                              d_state + 8, 1, 1, 1));
-    YA_HIP(ctx, hipMemcpyAsync(out, d_state + 8, 32, hipMemcpyDeviceToHost, ctx->stream));
-    YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(hs->state, out, 32); // the handle changes only after the device call succeeded
-    return YAMS_OK;
-}
-yams_status_t flush_whole_blocks(HashStream* hs) {
-    const size_t whole = hs->pending.size() / 64 * 64;
-    if (whole == 0) return YAMS_OK;
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    YA_TRY(stream_blocks(w.v, hs, hs->pending.data(), whole));
-    hs->pending.erase(hs->pending.begin(), hs->pending.begin() + static_cast<std::ptrdiff_t>(whole));
-    return YAMS_OK;
-}
-
-yams_status_t ch_stream_create(void*, void** out) {
-    NEED_INIT();
-    if (!out) return YAMS_ERR_INVALID_ARG;
-    auto* hs = new HashStream();
-    std::memcpy(hs->state, kShaInit, 32);
-    *out = hs;
-    return YAMS_OK;
-}
-yams_status_t ch_stream_init(void*, void* s) {
-    NEED_INIT();
-    if (!s) return YAMS_ERR_INVALID_ARG;
-    auto* hs = static_cast<HashStream*>(s);
-    std::memcpy(hs->state, kShaInit, 32);
-    hs->pending.clear(); hs->total = 0;
-    return YAMS_OK;
-}
-yams_status_t ch_stream_update(void*, void* s, const uint8_t* data, size_t n) {
-    NEED_INIT();
-    if (!s || (n && !data)) return YAMS_ERR_INVALID_ARG;
-    auto* hs = static_cast<HashStream*>(s);
-    size_t pos = 0;
-    while (pos < n) { // bounded host buffer: flush whole blocks every kStreamFlush bytes
-        const size_t take = std::min(n - pos, kStreamFlush - std::min(kStreamFlush, hs->pending.size()) + 64);
-        hs->pending.insert(hs->pending.end(), data + pos, data + pos + take);
-        hs->total += take;
-        pos += take;
-        if (hs->pending.size() >= kStreamFlush) {
-            const yams_status_t st = flush_whole_blocks(hs);
-            if (st != YAMS_OK) return st;
-        }
-    }
-    return YAMS_OK;
-}
-yams_status_t ch_stream_finalize(void*, void* s, char out_hex[65]) {
-    NEED_INIT();
-    if (!s || !out_hex) return YAMS_ERR_INVALID_ARG;
-    auto* hs = static_cast<HashStream*>(s);
-    // padding: 0x80, zeros, the bit length as a big-endian 64-bit word
-    const uint64_t bits = hs->total * 8;
-    hs->pending.push_back(0x80);
-    while (hs->pending.size() % 64 != 56) hs->pending.push_back(0);
-    for (int i = 7; i >= 0; --i) hs->pending.push_back(static_cast<uint8_t>(bits >> (8 * i)));
-    const yams_status_t st = flush_whole_blocks(hs);
-    if (st != YAMS_OK) return st;
-    uint8_t digest[32];            // the state's words, big-endian
-    for (int i = 0; i < 32; ++i) digest[i] = static_cast<uint8_t>(hs->state[i / 4] >> (24 - 8 * (i % 4)));
-    to_hex(digest, out_hex);
-    // "Reset for potential reuse" (sha256_hasher.cpp:103-106)
-    std::memcpy(hs->state, kShaInit, 32);
-    hs->pending.clear(); hs->total = 0;
-    ++g.hashes;
-    return YAMS_OK;
-}
-void ch_stream_destroy(void*, void* s) { delete static_cast<HashStream*>(s); }
-
-yams_status_t ch_verify_many(void*, const uint8_t* const* msgs, const size_t* lens, const char* expected_hex,
-                             size_t n, uint8_t* out_valid) {
-    if (n == 0) return YAMS_OK;
-    if (!msgs || !lens || !expected_hex || !out_valid) return YAMS_ERR_INVALID_ARG;
-    if (!chains_suit_the_device(lens, n)) { ++g.refused_chains; return YAMS_ERR_UNSUPPORTED; }
-    std::vector<char> hex(n * 65);
-    {
-        NEED_INIT();
-        Lease<yams_accel_ctx*> w(g.work_ctx);
-        g.hashes += n;
-        yams_status_t s = yams_sha256_many_host(w.v, msgs, lens, n, hex.data());
-        if (s != YAMS_OK) return s;
-    }
-    for (size_t i = 0; i < n; ++i) { // the reference compares the lower-case hex strings (:243-249)
-        uint8_t a[32], b[32];
-        out_valid[i] = (parse_hex32(hex.data() + 65 * i, a) && parse_hex32(expected_hex + 65 * i, b) &&
-                        std::memcmp(a, b, 32) == 0) ? 1 : 0;
-    }
-    return YAMS_OK;
-}
-
-// Dedup sets: each owns a context (its table lives in that context's device memory) and a mutex.
-struct DedupEntry { yams_accel_ctx* ctx = nullptr; yams_dedup_set* set = nullptr; std::mutex mu; };
-std::mutex g_dedup_mu;
-std::map<uint64_t, std::shared_ptr<DedupEntry>> g_dedup;
-uint64_t g_next_dedup = 1;
-
-std::shared_ptr<DedupEntry> find_dedup(uint64_t id) {
-    std::lock_guard<std::mutex> lk(g_dedup_mu);
-    auto it = g_dedup.find(id);
-    return it == g_dedup.end() ? nullptr : it->second;
-}
-void destroy_dedup(DedupEntry& e) {
-    if (e.set) yams_dedup_set_destroy(e.set);
-    if (e.ctx) yams_accel_ctx_destroy(e.ctx);
-    e.set = nullptr; e.ctx = nullptr;
-}
-
-yams_status_t ch_dedup_create(void*, uint64_t expected, uint64_t* out_id) {
-    NEED_INIT();
-    if (!out_id) return YAMS_ERR_INVALID_ARG;
-    auto e = std::make_shared<DedupEntry>();
-    yams_status_t st = yams_accel_ctx_create(g.devices[0], nullptr, &e->ctx);
-    if (st != YAMS_OK) return st;
-    st = yams_dedup_set_create(e->ctx, expected, &e->set);
-    if (st != YAMS_OK) { destroy_dedup(*e); return st; }
-    std::lock_guard<std::mutex> lk(g_dedup_mu);
-    *out_id = g_next_dedup++;
-    g_dedup[*out_id] = e;
-    return YAMS_OK;
-}
-yams_status_t dedup_call(uint64_t id, const char* hashes_hex, size_t n, uint8_t* out, bool insert) {
-    NEED_INIT();
-    auto e = find_dedup(id);
-    if (!e) return YAMS_ERR_NOT_FOUND;
-    if (n == 0) return YAMS_OK;
-    if (!hashes_hex || !out) return YAMS_ERR_INVALID_ARG;
-    std::vector<uint8_t> raw(n * 32);
-    for (size_t i = 0; i < n; ++i)
-        if (!parse_hex32(hashes_hex + 65 * i, raw.data() + 32 * i)) return YAMS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (!e->set) return YAMS_ERR_NOT_FOUND;
-    return insert ? yams_dedup_insert_host(e->set, raw.data(), n, out, nullptr)
-                  : yams_dedup_probe_host(e->set, raw.data(), n, out);
-}
-yams_status_t ch_dedup_insert(void*, uint64_t id, const char* hex, size_t n, uint8_t* out) { return dedup_call(id, hex, n, out, true); }
-yams_status_t ch_dedup_contains(void*, uint64_t id, const char* hex, size_t n, uint8_t* out) { return dedup_call(id, hex, n, out, false); }
-yams_status_t ch_dedup_size(void*, uint64_t id, uint64_t* out_entries) {
-    NEED_INIT();
-    auto e = find_dedup(id);
-    if (!e) return YAMS_ERR_NOT_FOUND;
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (!e->set) return YAMS_ERR_NOT_FOUND;
-    return yams_dedup_set_size(e->set, out_entries);
-}
-yams_status_t ch_dedup_destroy(void*, uint64_t id) {
-    NEED_INIT();
-    std::shared_ptr<DedupEntry> e;
-    {
-        std::lock_guard<std::mutex> lk(g_dedup_mu);
-        auto it = g_dedup.find(id);
-        if (it == g_dedup.end()) return YAMS_ERR_NOT_FOUND;
-        e = it->second;
-        g_dedup.erase(it);
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    destroy_dedup(*e);
-    return YAMS_OK;
-}
-
-yams_content_hash_v1 g_content_hash = {YAMS_IFACE_CONTENT_HASH_V1_VERSION, nullptr, GUARDED(ch_hash),
-                                       GUARDED(ch_hash_many), GUARDED(ch_stream_create), GUARDED(ch_stream_init),
-                                       GUARDED(ch_stream_update), GUARDED(ch_stream_finalize), GUARDED(ch_stream_destroy),
-                                       GUARDED(ch_verify_many), GUARDED(ch_dedup_create), GUARDED(ch_dedup_insert),
-                                       GUARDED(ch_dedup_contains), GUARDED(ch_dedup_size), GUARDED(ch_dedup_destroy)};
-
-// ---- topology_route_v1: the cluster router's dense signal over a resident index (yams_route_index_* / yams_route_dense_host) ----
-// Route indexes: each owns a context (its table lives in that context's device memory, its calls use that context's workspace)
-// and a mutex — the shape of the dedup sets above.
-struct RouteEntry { yams_accel_ctx* ctx = nullptr; yams_route_index* index = nullptr; std::mutex mu; };
-std::mutex g_route_mu;
-std::map<uint64_t, std::shared_ptr<RouteEntry>> g_route;
-uint64_t g_next_route = 1;
-
-void destroy_route(RouteEntry& e) {
-    if (e.index) yams_route_index_destroy(e.index);
-    if (e.ctx) yams_accel_ctx_destroy(e.ctx);
-    e.index = nullptr; e.ctx = nullptr;
-}
-std::shared_ptr<RouteEntry> find_route(uint64_t id) {
-    std::lock_guard<std::mutex> lk(g_route_mu);
-    auto it = g_route.find(id);
-    return it == g_route.end() ? nullptr : it->second;
-}
-
-yams_status_t tr_index_create(void*, const float* vectors, uint64_t n_vectors, uint32_t dim, const uint32_t* cluster_offsets,
-                              const uint8_t* has_centroid, const uint16_t* position, uint32_t n_clusters, uint64_t* out_id, float* out_norms) {
-    NEED_INIT();
-    if (!out_id) return YAMS_ERR_INVALID_ARG;
-    auto e = std::make_shared<RouteEntry>();
-    yams_status_t st = yams_accel_ctx_create(g.devices[0], nullptr, &e->ctx);
-    if (st != YAMS_OK) return st;
-    st = yams_route_index_create_host(e->ctx, vectors, n_vectors, dim, cluster_offsets, has_centroid, position, n_clusters, &e->index, out_norms);
-    if (st != YAMS_OK) { destroy_route(*e); return st; }
-    std::lock_guard<std::mutex> lk(g_route_mu);
-    *out_id = g_next_route++;
-    g_route[*out_id] = e;
-    return YAMS_OK;
-}
-yams_status_t tr_index_info(void*, uint64_t id, yams_route_index_info_t* out_info) {
-    NEED_INIT();
-    auto e = find_route(id);
-    if (!e) return YAMS_ERR_NOT_FOUND;
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (!e->index) return YAMS_ERR_NOT_FOUND;
-    return yams_route_index_info(e->index, out_info);
-}
-yams_status_t tr_dense(void*, uint64_t id, const float* queries, uint32_t n_queries, uint32_t rep_limit, const uint32_t* candidates,
-                       float* out_dense, uint8_t* out_observed, uint32_t* out_evals, yams_route_diag_t* out_diag) {
-    NEED_INIT();
-    auto e = find_route(id);
-    if (!e) return YAMS_ERR_NOT_FOUND;
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (!e->index) return YAMS_ERR_NOT_FOUND;
-    return yams_route_dense_host(e->index, queries, n_queries, rep_limit, candidates, out_dense, out_observed, out_evals, out_diag);
-}
-yams_status_t tr_index_destroy(void*, uint64_t id) {
-    NEED_INIT();
-    std::shared_ptr<RouteEntry> e;
-    {
-        std::lock_guard<std::mutex> lk(g_route_mu);
-        auto it = g_route.find(id);
-        if (it == g_route.end()) return YAMS_ERR_NOT_FOUND;
-        e = it->second;
-        g_route.erase(it);
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    destroy_route(*e);
-    return YAMS_OK;
-}
-
-yams_topology_route_v1 g_topology_route = {YAMS_IFACE_TOPOLOGY_ROUTE_V1_VERSION, nullptr, GUARDED(tr_index_create), GUARDED(tr_index_info),
-                                           GUARDED(tr_dense), GUARDED(tr_index_destroy)};
-
-// ---- topology_quality_v1: computePersistenceH0 over host memory (yams_quality_persistence_h0_host) --------------------------
-// the limits bound the arrays allocated here; every other check is the flat entry's
-yams_status_t tq_persistence_h0(void*, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select,
-                                uint32_t form, yams_persistence_h0_t* out, double** out_distances, double** out_merge_weights) {
-    NEED_INIT();
-    if (!out) return YAMS_ERR_INVALID_ARG;
-    const uint64_t m = select ? n_select : n;
-    if (m > YAMS_QUALITY_MAX_POINTS || dim > YAMS_CLUSTER_MAX_DIM || n >= (1ull << 31)) return YAMS_ERR_UNSUPPORTED;
-    double* dist = nullptr; double* w = nullptr;
-    if (out_distances && m) dist = static_cast<double*>(std::malloc(static_cast<size_t>(m) * m * 8));
-    if (out_merge_weights && m >= 2) w = static_cast<double*>(std::malloc(static_cast<size_t>(m - 1) * 8));
-    if ((out_distances && m && !dist) || (out_merge_weights && m >= 2 && !w)) { std::free(dist); std::free(w); return YAMS_ERR_RESOURCE_EXHAUSTED; }
-    yams_persistence_h0_t res{};
-    yams_status_t st;
-    {
-        Lease<yams_accel_ctx*> lease(g.work_ctx);
-        st = yams_quality_persistence_h0_host(lease.v, rows, n, dim, select, n_select, form, &res, dist, w, nullptr);
-    }
-    if (st != YAMS_OK) { std::free(dist); std::free(w); return st; }
-    *out = res;
-    if (out_distances) *out_distances = dist;
-    if (out_merge_weights) *out_merge_weights = w;
-    return YAMS_OK;
-}
-void tq_free_persistence_h0(void*, double* distances, double* merge_weights) { std::free(distances); std::free(merge_weights); }
-
-yams_topology_quality_v1 g_topology_quality = {YAMS_IFACE_TOPOLOGY_QUALITY_V1_VERSION, nullptr, GUARDED(tq_persistence_h0),
-                                               GUARDED(tq_free_persistence_h0)};
-
-// ---- topology_features_v1: the topology build's input features over host memory (yams_features_*_host) ----------------------
-// every output is the caller's array: every check is the flat entry's
-yams_status_t tf_aggregate(void*, const float* rows, uint64_t n_records, uint32_t dim, const uint64_t* doc_offsets, const uint32_t* records,
-                           uint64_t n_docs, float* out, uint32_t* out_counts) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    return yams_features_aggregate_host(lease.v, rows, n_records, dim, doc_offsets, records, n_docs, out, out_counts);
-}
-yams_status_t tf_variance(void*, const float* rows, uint64_t n, uint32_t dim, const uint32_t* select, uint64_t n_select, uint32_t form,
-                          double* out_mean, double* out_var) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    return yams_features_variance_host(lease.v, rows, n, dim, select, n_select, form, out_mean, out_var);
-}
-yams_status_t tf_compose(void*, const float* dense, uint64_t n, uint32_t dim, const float* weights, const float* entity, uint32_t k,
-                         const uint8_t* entity_on, const uint32_t* sig, uint32_t sig_len, const uint8_t* sketch_on, uint32_t sketch_dim,
-                         float alpha_e, float alpha_m, float* out, uint32_t out_stride, uint32_t* out_dims) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    return yams_features_compose_host(lease.v, dense, n, dim, weights, entity, k, entity_on, sig, sig_len, sketch_on, sketch_dim, alpha_e,
-                                      alpha_m, out, out_stride, out_dims);
-}
-
-yams_topology_features_v1 g_topology_features = {YAMS_IFACE_TOPOLOGY_FEATURES_V1_VERSION, nullptr, GUARDED(tf_aggregate), GUARDED(tf_variance),
-                                                 GUARDED(tf_compose)};
-
-// ---- late_interaction_rerank_v1: ColBERT MaxSim and token pooling over host memory (yams_rerank_*_host) ----------------------
-// every output is the caller's array: every check is the flat entry's
-yams_status_t lr_maxsim(void*, const float* query, uint32_t tq, uint32_t dim, const float* rows, const uint64_t* doc_offsets, uint64_t n_docs,
-                        uint32_t form, float* out_scores, float* out_rowmax, uint32_t* out_rowarg, yams_rerank_diag_t* diag) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    return yams_rerank_maxsim_host(lease.v, query, tq, dim, rows, doc_offsets, n_docs, form, out_scores, out_rowmax, out_rowarg, diag);
-}
-yams_status_t lr_maxpool(void*, const float* rows, uint32_t dim, const uint64_t* doc_offsets, uint64_t n_docs, float* out) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    return yams_rerank_maxpool_host(lease.v, rows, dim, doc_offsets, n_docs, out);
-}
-
-yams_late_interaction_rerank_v1 g_late_rerank = {YAMS_IFACE_LATE_INTERACTION_RERANK_V1_VERSION, nullptr, GUARDED(lr_maxsim), GUARDED(lr_maxpool)};
-
-// ---- embedding_pool_v1: the embedding model's pooling head (yams_embed_*), over host memory or over device addresses -----------
-// every output is the caller's array: every check is the flat entry's
-yams_status_t ep_pool(void*, const float* hidden, uint64_t batch, uint32_t seq, uint32_t dim, const int32_t* mask, uint32_t mask_len,
-                      uint32_t mode, uint32_t flags, float* out, yams_embed_diag_t* diag) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    return yams_embed_pool_host(lease.v, hidden, batch, seq, dim, mask, mask_len, mode, flags, out, diag);
-}
-yams_status_t ep_normalize(void*, const float* rows, uint64_t batch, uint32_t dim, float* out) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    return yams_embed_normalize_host(lease.v, rows, batch, dim, out);
-}
-// the hidden states (the rows) at a DEVICE address, everything else in host memory: the mask goes up, the B * dim result comes back
-yams_status_t ep_pool_device(void*, const float* hidden, uint64_t batch, uint32_t seq, uint32_t dim, const int32_t* mask, uint32_t mask_len,
-                             uint32_t mode, uint32_t flags, float* out, yams_embed_diag_t* diag) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    yams_accel_ctx* ctx = lease.v;
-    // what the flat entry refuses (or, batch == 0, answers) before it looks at a mask or an output: its verdict, nothing is staged
-    if (batch == 0 || !out || dim == 0 || seq == 0 || dim > YAMS_EMBED_MAX_DIM || seq > YAMS_EMBED_MAX_SEQ || batch > YAMS_EMBED_MAX_ROWS / seq)
-        return yams_embed_pool_device(ctx, hidden, batch, seq, dim, nullptr, mask_len, mode, flags, out, diag);
-    // only the considered columns of the mask go up: at most batch * seq values
-    if (mode == YAMS_EMBED_POOL_CLS) mask = nullptr;
-    const uint32_t cols = mask_len < seq ? mask_len : seq;
-    const size_t mb = mask ? static_cast<size_t>(batch) * cols * 4 : 0, ob = static_cast<size_t>(batch) * dim * 4;
-    int32_t* d_mask = nullptr; float* d_out;
-    if (mb) YA_TRY(yams_accel::ws_get(ctx, "embed_door_mask", mb, (void**)&d_mask));
-    YA_TRY(yams_accel::ws_get(ctx, "embed_door_out", ob, (void**)&d_out));
-    if (mb && cols == mask_len) YA_HIP(ctx, yams_accel::staged_h2d(d_mask, mask, mb, ctx->stream));
-    else if (mb) YA_HIP(ctx, hipMemcpy2DAsync(d_mask, static_cast<size_t>(cols) * 4, mask, static_cast<size_t>(mask_len) * 4, static_cast<size_t>(cols) * 4, batch, hipMemcpyHostToDevice, ctx->stream));
-    if (mask && !mb) mask_len = 0;
-    else if (mask) mask_len = cols;
-    YA_TRY(yams_embed_pool_device(ctx, hidden, batch, seq, dim, d_mask, mask_len, mode, flags, d_out, diag));
-    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
-    YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return YAMS_OK;
-}
-yams_status_t ep_normalize_device(void*, const float* rows, uint64_t batch, uint32_t dim, float* out) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> lease(g.work_ctx);
-    yams_accel_ctx* ctx = lease.v;
-    if (batch == 0 || !out || dim == 0 || dim > YAMS_EMBED_MAX_DIM || batch > YAMS_EMBED_MAX_ROWS)
-        return yams_embed_normalize_device(ctx, rows, batch, dim, out);      // its verdict; nothing is staged
-    const size_t ob = static_cast<size_t>(batch) * dim * 4;
-    float* d_out;
-    YA_TRY(yams_accel::ws_get(ctx, "embed_door_out", ob, (void**)&d_out));
-    YA_TRY(yams_embed_normalize_device(ctx, rows, batch, dim, d_out));
-    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
-    YA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return YAMS_OK;
-}
-
-yams_embedding_pool_v1 g_embedding_pool = {YAMS_IFACE_EMBEDDING_POOL_V1_VERSION, nullptr, GUARDED(ep_pool), GUARDED(ep_normalize),
-                                           GUARDED(ep_pool_device), GUARDED(ep_normalize_device)};
-
-// ---- content_checksum_v1: the compressed store's CRC-32 over host memory (yams_crc32_many_host) ------------------------------
-yams_status_t cs_crc32_many(void*, const uint8_t* const* msgs, const size_t* lens, size_t n, uint32_t* out) {
-    NEED_INIT();
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    return yams_crc32_many_host(w.v, msgs, lens, n, out);
-}
-yams_status_t cs_crc32(void*, const uint8_t* data, size_t n, uint32_t* out) {
-    NEED_INIT();
-    if (!out || (n && !data)) return YAMS_ERR_INVALID_ARG;
-    const uint8_t* msgs[1] = {data};
-    const size_t lens[1] = {n};
-    Lease<yams_accel_ctx*> w(g.work_ctx);
-    return yams_crc32_many_host(w.v, msgs, lens, 1, out);
-}
-yams_status_t cs_verify_many(void*, const uint8_t* const* msgs, const size_t* lens, const uint32_t* expected, size_t n, uint8_t* out_valid) {
-    NEED_INIT();
-    if (n == 0) return YAMS_OK;
-    if (!msgs || !lens || !expected || !out_valid) return YAMS_ERR_INVALID_ARG;
-    std::vector<uint32_t> got(n);
-    {
-        Lease<yams_accel_ctx*> w(g.work_ctx);
-        const yams_status_t s = yams_crc32_many_host(w.v, msgs, lens, n, got.data());
-        if (s != YAMS_OK) return s;
-    }
-    for (size_t i = 0; i < n; ++i) out_valid[i] = got[i] == expected[i] ? 1 : 0;
-    return YAMS_OK;
-}
-
-yams_content_checksum_v1 g_content_checksum = {YAMS_IFACE_CONTENT_CHECKSUM_V1_VERSION, nullptr, GUARDED(cs_crc32), GUARDED(cs_crc32_many),
-                                               GUARDED(cs_verify_many)};
-
-// ---- chunker_v1 -------------------------------------------------------------------------------
-yams_status_t ck_default_config(void*, uint32_t mode, yams_cdc_config_t* out_cfg) {
-    if (!out_cfg || (mode != YAMS_CDC_RABIN && mode != YAMS_CDC_STREAMING)) return YAMS_ERR_INVALID_ARG;
-    yams_cdc_default_config(out_cfg, mode);
-    return YAMS_OK;
-}
-// re-entrant: ContentStore shares one chunker across its workers (content_store_impl.cpp:1412)
-// One buffer; the first context_len bytes are history (chunk_window: a window of a stream), 0 for chunk_data.
-yams_status_t ck_chunk_window(void*, const uint8_t* data, size_t n, size_t context_len, const yams_cdc_config_t* cfg,
-                              yams_chunk_ref_t** out_chunks, size_t* out_count) {
-    NEED_INIT();
-    if (!out_chunks || !out_count || !cfg) return YAMS_ERR_INVALID_ARG;
-    *out_chunks = nullptr; *out_count = 0;
-    const uint64_t floor = std::max<uint64_t>(1, cfg->min_size);
-    size_t cap = n / floor + 2;
-    std::vector<uint64_t> off(cap), sz(cap);
-    std::vector<char> hex(cap * 65);
-    size_t cnt = 0;
-    yams_status_t s;
-    {
-        Lease<yams_accel_ctx*> w(g.work_ctx);
-        s = yams_cdc_chunk_window_host(w.v, data, n, context_len, cfg, off.data(), sz.data(), hex.data(), cap, &cnt);
-    }
-    if (s != YAMS_OK) return s;
-    auto* chunks = static_cast<yams_chunk_ref_t*>(std::calloc(std::max<size_t>(cnt, 1), sizeof(yams_chunk_ref_t)));
-    if (!chunks) return YAMS_ERR_INTERNAL;
-    for (size_t i = 0; i < cnt; ++i) {
-        chunks[i].offset = off[i]; chunks[i].size = sz[i];
-        std::memcpy(chunks[i].hash_hex, hex.data() + 65 * i, 65);
-    }
-    ++g.chunk_calls;
-    *out_chunks = chunks; *out_count = cnt;
-    return YAMS_OK;
-}
-yams_status_t ck_chunk_data(void* self, const uint8_t* data, size_t n, const yams_cdc_config_t* cfg,
-                            yams_chunk_ref_t** out_chunks, size_t* out_count) {
-    return ck_chunk_window(self, data, n, 0, cfg, out_chunks, out_count);
-}
-void ck_free_chunks(void*, yams_chunk_ref_t* chunks, size_t) { std::free(chunks); }
-
-void ck_free_chunk_batch(void*, yams_chunk_batch_t* b) {
-    if (!b) return;
-    std::free(b->first_chunk); std::free(b->chunks); std::free(b->buffer_hash_hex); std::free(b);
-}
-// Many buffers per call: the batched ingest path (yams_ingest_host) behind the plugin door.
-yams_status_t ck_chunk_many(void*, const uint8_t* const* buffers, const size_t* lens, size_t n, const yams_cdc_config_t* cfg,
-                            uint32_t flags, yams_chunk_batch_t** out_batch) {
-    NEED_INIT();
-    if (!out_batch) return YAMS_ERR_INVALID_ARG;
-    *out_batch = nullptr;
-    if (!cfg || (n && (!buffers || !lens))) return YAMS_ERR_INVALID_ARG;
-    const bool want_blob = (flags & YAMS_CHUNK_MANY_BUFFER_HASHES) != 0;
-    const bool defer = want_blob && (flags & YAMS_CHUNK_MANY_DEFER_LONG_BUFFER_HASHES) != 0;
-    // First guess of the chunk count: one chunk per `floor` bytes, where floor is the smallest chunk the configuration
-    // can emit in the common case — min(min, max), but never below 256 bytes (min_size == 0 is a legal configuration:
-    // a per-byte bound would be ~48 bytes of host vectors per input byte).  Should the guess be too low (min > max, or
-    // a degenerate mask) yams_ingest_host reports the required size and the call runs once more with exactly that.
-    uint64_t floor = std::min<uint64_t>(cfg->min_size ? cfg->min_size : cfg->max_size, cfg->max_size ? cfg->max_size : cfg->min_size);
-    floor = std::max<uint64_t>(floor, 256);
-    std::vector<uint64_t> len64(n);
-    uint64_t cap = 0, total = 0;
-    for (size_t i = 0; i < n; ++i) { len64[i] = lens[i]; cap += lens[i] / floor + 2; total += lens[i]; }
-    std::vector<uint64_t> first(n + 1, 0), off, sz;
-    std::vector<uint8_t> dig, bdig(want_blob ? n * 32 : 0);
-    uint64_t cnt = 0;
-    if (n) {
-        Lease<yams_accel_ctx*> w(g.work_ctx);
-        for (int attempt = 0; ; ++attempt) {
-            off.assign(cap, 0); sz.assign(cap, 0); dig.assign(cap * 32, 0);
-            const yams_status_t s = yams_ingest_host(w.v, buffers, len64.data(), n, cfg,
-                                                     YAMS_INGEST_CHUNK_DIGESTS | (want_blob ? YAMS_INGEST_BLOB_DIGESTS : 0u) |
-                                                         (defer ? YAMS_INGEST_DEFER_LONG_BLOB_DIGESTS : 0u), 0,
-                                                     first.data(), off.data(), sz.data(), dig.data(), cap,
-                                                     want_blob ? bdig.data() : nullptr, &cnt);
-            if (s == YAMS_OK) break;
-            if (s == YAMS_ERR_INVALID_ARG && attempt == 0 && cnt > cap) { cap = cnt; continue; } // "chunk arrays too small": cnt is the required size
-            return s;
-        }
-    }
-    const uint64_t defer_above = defer ? yams_ingest_defer_threshold_host(total) : UINT64_MAX;
-    auto* b = static_cast<yams_chunk_batch_t*>(std::calloc(1, sizeof(yams_chunk_batch_t)));
-    if (!b) return YAMS_ERR_INTERNAL;
-    b->n_buffers = n; b->n_chunks = static_cast<size_t>(cnt);
-    b->first_chunk = static_cast<size_t*>(std::calloc(n + 1, sizeof(size_t)));
-    b->chunks = static_cast<yams_chunk_ref_t*>(std::calloc(std::max<size_t>(b->n_chunks, 1), sizeof(yams_chunk_ref_t)));
-    b->buffer_hash_hex = want_blob ? static_cast<char*>(std::calloc(std::max<size_t>(n, 1), 65)) : nullptr;
-    if (!b->first_chunk || !b->chunks || (want_blob && !b->buffer_hash_hex)) { ck_free_chunk_batch(nullptr, b); return YAMS_ERR_INTERNAL; }
-    for (size_t i = 0; i <= n; ++i) b->first_chunk[i] = static_cast<size_t>(first[i]);
-    for (size_t i = 0; i < b->n_chunks; ++i) {
-        b->chunks[i].offset = off[i]; b->chunks[i].size = sz[i];
-        to_hex(dig.data() + 32 * i, b->chunks[i].hash_hex);
-    }
-    if (want_blob)
-        for (size_t i = 0; i < n; ++i) {
-            if (len64[i] > defer_above) { ++g.deferred_chains; continue; } // (calloc'd: the entry stays empty — the host's hasher fills it)
-            to_hex(bdig.data() + 32 * i, b->buffer_hash_hex + 65 * i);
-        }
-    g.chunk_calls += n;
-    *out_batch = b;
-    return YAMS_OK;
-}
-
-yams_chunker_v1 g_chunker = {YAMS_IFACE_CHUNKER_V1_VERSION, nullptr, GUARDED(ck_default_config),
-                             GUARDED(ck_chunk_data), GUARDED(ck_free_chunks), GUARDED(ck_chunk_many),
-                             GUARDED(ck_free_chunk_batch), GUARDED(ck_chunk_window)};
+                                                   GUARDED(es_search_entities), GUARDED(free_arrays<yams_scan_hit_t, uint32_t>)};
 
 void teardown_locked() { // g.mu held exclusively
-    {
-        std::lock_guard<std::mutex> lk(g.corpora_mu);
-        for (auto& kv : g.corpora) { std::unique_lock<std::shared_mutex> cl(kv.second->mu); release_corpus(*kv.second); }
-        g.corpora.clear();
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_dedup_mu);
-        for (auto& kv : g_dedup) { std::lock_guard<std::mutex> el(kv.second->mu); destroy_dedup(*kv.second); }
-        g_dedup.clear();
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_route_mu);
-        for (auto& kv : g_route) { std::lock_guard<std::mutex> el(kv.second->mu); destroy_route(*kv.second); }
-        g_route.clear();
-    }
+    g.corpora.drain(release_corpus);
+    teardown_content();      // the dedup sets
+    teardown_topology();     // the route indexes
     if (g.sharded) yams_scan_sharded_destroy(g.sharded);
     g.sharded = nullptr;
     for (auto* c : g.work_ctx.drain()) yams_accel_ctx_destroy(c);
@@ -1730,6 +677,10 @@ void teardown_locked() { // g.mu held exclusively
 }
 
 } // namespace
+} // namespace door
+} // namespace yams_accel
+
+using namespace yams_accel::door;
 
 extern "C" {
 
@@ -1869,25 +820,18 @@ static int plugin_health_impl(char** out_json) {
     if (!out_json) return YAMS_PLUGIN_ERR_INVALID;
     std::shared_lock<std::shared_mutex> lk(g.mu);
     std::ostringstream os;
-    size_t n_corpora;
     // device memory behind the mirrors: mapped into live corpora, and parked (mappings of destroyed corpora waiting for
     // the next one) — what an allocation-failure test watches for leaks
     uint64_t mirror_mapped = 0, mirror_parked = 0;
     size_t rotated_corpora = 0;
-    {
-        std::lock_guard<std::mutex> cl(g.corpora_mu);
-        n_corpora = g.corpora.size();
-        for (auto& kv : g.corpora) {
-            rotated_corpora += kv.second->i8_flags > 0 && (kv.second->i8_flags & static_cast<int>(YAMS_SCAN_I8_ROTATED));
-            for (auto& s : kv.second->sh)
-                for (const GrowBuf* b : {&s.rows, &s.bf16, &s.i8, &s.nsq, &s.i8meta, &s.tie, &s.inv}) mirror_mapped += b->mapped;
-            mirror_mapped += kv.second->rank_of_row.mapped;
-        }
-    }
-    {
-        std::lock_guard<std::mutex> pl(g_park_mu);
-        for (auto& kv : g_parked) for (auto& b : kv.second) mirror_parked += b.mapped;
-    }
+    const size_t n_corpora = g.corpora.size();
+    g.corpora.visit([&](const Corpus& c) {
+        rotated_corpora += c.i8_flags > 0 && (c.i8_flags & static_cast<int>(YAMS_SCAN_I8_ROTATED));
+        for (auto& s : c.sh)
+            for (const GrowBuf* b : {&s.rows, &s.bf16, &s.i8, &s.nsq, &s.i8meta, &s.tie, &s.inv}) mirror_mapped += b->mapped;
+        mirror_mapped += c.rank_of_row.mapped;
+    });
+    mirror_parked = GrowBuf::parked_bytes();
     os << "{\"status\":\"" << (g.initialised ? "ok" : "not_initialised") << "\",\"devices\":[";
     for (size_t i = 0; i < g.devices.size(); ++i) os << (i ? "," : "") << g.devices[i];
     os << "],\"device\":" << (g.devices.empty() ? 0 : g.devices[0]) << ",\"search_slots\":" << g.search_slots

@@ -2,7 +2,8 @@
 //
 // What the door computes on the host before and after a device call: the strict reader of its configuration, the dealing
 // of rows, allow-masks and tie ranks to the shards of a striped corpus, the ranking of the PQ engine's keys, the packing of
-// hits, hex.  No HIP call and no global: the stripe width is a parameter, and the local -> global direction of the dealing
+// hits, hex — and the door's two ownership rules: the malloc'd arrays a call hands out (OwnedArrays, HitResult) and the registry
+// of a handle family (HandleTable).  No HIP call and no global: the stripe width is a parameter, and the local -> global direction of the dealing
 // is contract_rules.h's global_row_id, the function the kernels undo the dealing with.  Compiles with g++ -std=c++17 and no
 // ROCm include path; tests/cpp/plugin_host_test.cpp holds every function here on the CPU, under ASan and UBSan.
 #pragma once
@@ -10,8 +11,11 @@
 #include <cctype>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 #include <map>
+#include <memory>
+#include <mutex>
 #include <numeric>
 #include <set>
 #include <string>
@@ -234,6 +238,95 @@ inline void pack_hits(uint32_t nq, uint32_t k, const uint32_t* counts, const int
             else { hits[o].row = -1; hits[o].similarity = 0.f; hits[o].distance = 0.f; }
         }
 }
+
+// ---- what a door hands to its caller: malloc'd arrays that go with the object unless they are committed -------------------
+// add() allocates count elements behind the out parameter `out` (not wanted: no array, the out parameter still gets its null;
+// a wanted array of no elements is one byte, never a null that reads as a failure); ok() is false once a wanted allocation
+// failed or its size overflows size_t.  commit() writes every array to its out parameter (a null out parameter is skipped)
+// and lets go of them: the caller frees them through the vtable's free function.  What was not committed is freed here, so a
+// door returns from any failure as it stands and its out parameters stay as it left them.
+class OwnedArrays {
+public:
+    OwnedArrays() = default;
+    OwnedArrays(const OwnedArrays&) = delete;
+    OwnedArrays& operator=(const OwnedArrays&) = delete;
+    ~OwnedArrays() { for (const Slot& s : slots_) std::free(s.p); }
+    template <typename T> T* add(T** out, size_t count, bool wanted = true) {
+        slots_.push_back(Slot{nullptr, out});      // (first: an array is never without its slot)
+        if (!wanted) return nullptr;
+        if (count > SIZE_MAX / sizeof(T)) { ok_ = false; return nullptr; }
+        slots_.back().p = std::malloc(std::max<size_t>(count * sizeof(T), 1));
+        if (!slots_.back().p) ok_ = false;
+        return static_cast<T*>(slots_.back().p);
+    }
+    bool ok() const { return ok_; }
+    yams_status_t commit() {
+        for (const Slot& s : slots_) if (s.out) std::memcpy(s.out, &s.p, sizeof s.p);      // (*out = p, whatever the element type)
+        slots_.clear();
+        return YAMS_OK;
+    }
+private:
+    struct Slot { void* p; void* out; };
+    std::vector<Slot> slots_;
+    bool ok_ = true;
+};
+
+// The malloc'd result of a search: hits[nq * max(k, 1)], every row preset to -1, and counts[max(nq, 1)], zeroed.  commit()
+// hands both to the caller (who frees them through the vtable's free function); what was not committed goes with the object.
+// (The same rule as OwnedArrays; written out, because its two arrays are calloc'd and preset.)
+struct HitResult {
+    const size_t slots;
+    uint32_t* counts;
+    yams_scan_hit_t* hits;
+    HitResult(uint32_t nq, uint32_t k)
+        : slots(static_cast<size_t>(nq) * std::max<uint32_t>(k, 1)),
+          counts(static_cast<uint32_t*>(std::calloc(std::max<uint32_t>(nq, 1), sizeof(uint32_t)))),
+          hits(static_cast<yams_scan_hit_t*>(std::calloc(std::max<size_t>(slots, 1), sizeof(yams_scan_hit_t)))) {
+        for (size_t o = 0; hits && o < slots; ++o) hits[o].row = -1;
+    }
+    HitResult(const HitResult&) = delete;
+    ~HitResult() { std::free(counts); std::free(hits); }
+    bool ok() const { return counts && hits; }
+    yams_status_t commit(yams_scan_hit_t** out_hits, uint32_t** out_counts) {
+        *out_hits = hits; *out_counts = counts;
+        hits = nullptr; counts = nullptr;
+        return YAMS_OK;
+    }
+};
+
+// ---- the registry of a handle family: id -> entry ---------------------------------------------------------------------------
+// Ids start at 1 and are never reused within the table's life (not after take(), not after drain(): an id a host kept
+// across a shutdown names nothing afterwards).  An Entry carries its own mutex `mu` and its payload.  find() and take() hand
+// out a shared_ptr, so an entry outlives its removal for as long as a call holds it: whoever took it locks `mu` and destroys
+// the payload; a call that found it earlier locks `mu`, sees the payload gone and answers NOT_FOUND.
+template <typename Entry> class HandleTable {
+public:
+    uint64_t insert(std::shared_ptr<Entry> e) { std::lock_guard<std::mutex> lk(mu_); map_[next_] = std::move(e); return next_++; }
+    std::shared_ptr<Entry> find(uint64_t id) { return get(id, false); }
+    std::shared_ptr<Entry> take(uint64_t id) { return get(id, true); }      // removed; its contents are the caller's to destroy, under the entry's mu
+    template <typename F> void drain(F&& destroy) {   // teardown: every entry, locked; the table is empty afterwards
+        std::lock_guard<std::mutex> lk(mu_);
+        for (auto& kv : map_) { std::unique_lock<decltype(kv.second->mu)> el(kv.second->mu); destroy(*kv.second); }
+        map_.clear();
+    }
+    template <typename F> void visit(F&& look) {      // every entry, NOT locked: for figures that may be a moment old
+        std::lock_guard<std::mutex> lk(mu_);
+        for (auto& kv : map_) look(*kv.second);
+    }
+    size_t size() { std::lock_guard<std::mutex> lk(mu_); return map_.size(); }
+private:
+    std::shared_ptr<Entry> get(uint64_t id, bool remove) {
+        std::lock_guard<std::mutex> lk(mu_);
+        const auto it = map_.find(id);
+        if (it == map_.end()) return nullptr;
+        std::shared_ptr<Entry> e = it->second;
+        if (remove) map_.erase(it);
+        return e;
+    }
+    std::mutex mu_;
+    std::map<uint64_t, std::shared_ptr<Entry>> map_;
+    uint64_t next_ = 1;
+};
 
 // One SHA-256 chain is sequential: ~35 MB/s on a device lane, > 1 GB/s on a host core.  Work the device is worse
 // at is refused (YAMS_ERR_UNSUPPORTED: the host hashes it itself), not served slowly — see the public header.
