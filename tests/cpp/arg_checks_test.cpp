@@ -1,6 +1,7 @@
 // arg_checks_test.cpp — yams_amd/csrc/arg_checks.h (the argument checks that need neither the device nor a context) held to its
 // definitions on the CPU.  A stand-alone program: plain g++ with AddressSanitizer and UBSan, no ROCm include path.  The offsets
-// arrays live on the heap with exactly lists + 1 entries, so a read past one ends the run.
+// arrays live on the heap with exactly lists + 1 entries, the index lists, rows and packed rows with exactly their contracted
+// lengths, so a read or write past one ends the run.
 #include <cstdint>
 #include <cstdio>
 #include <memory>
@@ -8,6 +9,8 @@
 
 #include "../../yams_amd/csrc/arg_checks.h"
 
+using yams_accel::gather_rows;
+using yams_accel::indices_below;
 using yams_accel::offsets_ascend;
 using yams_accel::overlaps;
 
@@ -81,9 +84,65 @@ static void test_offsets() {
     CHECK(ascend({0, ~0ull}));
 }
 
+// a heap copy of exactly v.size() entries (an allocation of no bytes for an empty list: any read of it ends the run)
+template <class T> static std::unique_ptr<T[]> exact(const std::vector<T>& v) {
+    std::unique_ptr<T[]> heap(new T[v.size()]);
+    for (size_t i = 0; i < v.size(); ++i) heap[i] = v[i];
+    return heap;
+}
+
+static bool below(const std::vector<uint32_t>& idx, uint64_t limit, bool allow_sentinel = false) {
+    return indices_below(exact(idx).get(), idx.size(), limit, allow_sentinel);
+}
+
+static void test_indices() {
+    // an empty list holds no index that could be out of range, whatever the limit
+    CHECK(below({}, 0));
+    CHECK(below({}, 5, true));
+    CHECK(indices_below(nullptr, 0, 0));
+    CHECK(below({0, 4, 2, 4}, 5));
+    // the last index equal to the limit; the first; one past it
+    CHECK(!below({0, 4, 2, 5}, 5));
+    CHECK(!below({5, 0}, 5));
+    CHECK(!below({0, 6, 1}, 5));
+    CHECK(!below({0}, 0));
+    // the sentinel: allowed only when asked for, and only that value
+    CHECK(below({0xffffffffu, 1, 0xffffffffu}, 2, true));
+    CHECK(!below({0xffffffffu, 1}, 2, false));
+    CHECK(!below({0xffffffffu, 1}, 2));
+    CHECK(!below({0xfffffffeu}, 2, true));
+    CHECK(!below({0xffffffffu, 2}, 2, true));
+    CHECK(indices_below(exact<uint32_t>({7, 2}).get(), 2, 3, true, 7));      // (a caller's own sentinel)
+    // a limit above 2^32 - 1 admits every uint32 (limits are the callers' uint64 row counts)
+    CHECK(below({0xffffffffu}, 1ull << 32));
+}
+
+// gather_rows over heap arrays of exactly the contracted lengths: rows [n][dim], select [m], packed [m][dim]
+static std::vector<float> gathered(const std::vector<float>& rows, uint32_t dim, const std::vector<uint32_t>& select) {
+    auto r = exact(rows);
+    auto s = exact(select);
+    std::unique_ptr<float[]> packed(new float[select.size() * dim]);
+    gather_rows(r.get(), dim, s.get(), select.size(), packed.get());
+    return std::vector<float>(packed.get(), packed.get() + select.size() * dim);
+}
+
+static void test_gather() {
+    const std::vector<float> rows = {0.f, 1.f, 2.f, 10.f, 11.f, 12.f, 20.f, 21.f, 22.f};      // [3][3]
+    // m == 0: nothing is read, nothing is written
+    CHECK(gathered(rows, 3, {}).empty());
+    CHECK(gathered({}, 3, {}).empty());
+    // the order of select is the order of packed; a repeated index is copied each time; the last row ends at the array's end
+    CHECK((gathered(rows, 3, {2, 0, 2, 2}) == std::vector<float>{20.f, 21.f, 22.f, 0.f, 1.f, 2.f, 20.f, 21.f, 22.f, 20.f, 21.f, 22.f}));
+    CHECK((gathered(rows, 3, {1}) == std::vector<float>{10.f, 11.f, 12.f}));
+    // dim == 1: the same array as nine rows of one value
+    CHECK((gathered(rows, 1, {8, 0, 8, 3}) == std::vector<float>{22.f, 0.f, 22.f, 10.f}));
+}
+
 int main() {
     test_overlaps();
     test_offsets();
+    test_indices();
+    test_gather();
     std::printf("%s (%d failures)\n", failures ? "FAILED" : "OK", failures);
     return failures ? 1 : 0;
 }

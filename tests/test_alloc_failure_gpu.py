@@ -201,3 +201,32 @@ def test_flat_entry_points_report_exhaustion(armed, oracle):
     s = acc.dedup_set(1000)
     s.close()
     acc.close()
+
+
+@needs_injection
+def test_a_host_twin_whose_staging_cannot_be_had_writes_nothing(armed):
+    """yams_cluster_centroids_host on a fresh context, where every staging slot is still to be allocated.  The counter is the
+    number of allocations that may still succeed: 0 refuses the first slot (the rows) before anything is enqueued, 1 lets the
+    rows be allocated and their upload be enqueued and refuses the second slot (the offsets).  Both times: status 7, the message
+    names the slot, and no output byte changes (the wrapper holds the guard pattern of a refused call).  Disarmed, the same
+    call serves and equals the device twin bit for bit."""
+    L = armed
+    from yams_amd.accel import Accel
+    acc = Accel(0)
+    rng = np.random.default_rng(5)
+    rows = rng.standard_normal((5, 3)).astype(np.float32)
+    off = np.array([0, 2, 2, 5], np.uint64)
+    members = np.array([4, 0, 1, 3, 2], np.uint32)
+    for may_succeed, slot in ((0, "art_host_rows"), (1, "art_host_offsets")):
+        before = L.yams_accel_debug_alloc_faults()
+        L.yams_accel_debug_fail_alloc_after(may_succeed)
+        with pytest.raises(_lib.AccelError) as e:
+            acc.cluster_centroids(rows, off, members, host_entry=True)
+        L.yams_accel_debug_fail_alloc_after(-1)
+        assert e.value.status == _lib.YAMS_ERR_RESOURCE_EXHAUSTED and f"hipMalloc workspace '{slot}'" in str(e.value), str(e.value)
+        assert L.yams_accel_debug_alloc_faults() == before + 1
+    cent_h, cnt_h = acc.cluster_centroids(rows, off, members, host_entry=True)
+    cent_d, cnt_d = acc.cluster_centroids(rows, off, members, host_entry=False)
+    assert np.array_equal(cent_h.view(np.uint32), cent_d.view(np.uint32)) and np.array_equal(cnt_h, cnt_d)
+    assert list(cnt_h) == [2, 0, 3]
+    acc.close()

@@ -551,23 +551,12 @@ class Accel:
             ke, it = self.cluster_kmeans_device(None, 0, dim, k, max_iterations)
             return np.zeros(0, np.uint32), np.zeros((0, dim), np.float32), ke, it
         kmax = self._effective_k(n, k)
-        if host_entry:
-            mem = np.zeros(n, np.uint32); cent = np.zeros((kmax, dim), np.float32)
-            ke = C.c_uint32(); it = C.c_uint32()
-            self._check(self.L.yams_cluster_kmeans_host(self.ctx, x.ctypes.data, n, dim, k, max_iterations, mem.ctypes.data, cent.ctypes.data,
-                                                        C.byref(ke), C.byref(it)))
-            return mem, cent[:ke.value], ke.value, it.value
-        d_x = self.to_device(x) if x.size else None
-        d_m = self.alloc(n * 4 + 16); d_c = self.alloc(kmax * dim * 4 + 16)
-        try:
-            ke, it = self.cluster_kmeans_device(d_x.ptr if d_x else None, n, dim, k, max_iterations, d_m.ptr, d_c.ptr)
-            mem = d_m.download(np.uint32, n)
-            cent = d_c.download(np.float32, ke * dim).reshape(ke, dim)
-        finally:
-            for b in (d_x, d_m, d_c):
-                if b is not None:
-                    b.free()
-        return mem, cent, ke, it
+        ke = C.c_uint32(); it = C.c_uint32()
+        mem, cent = self._artifact_call(
+            self.L.yams_cluster_kmeans_device, self.L.yams_cluster_kmeans_host, host_entry,
+            [x if x.size else None], [(np.uint32, n), (np.float32, kmax * dim)],
+            lambda i, o: (i[0], n, dim, k, max_iterations, o[0], o[1], C.byref(ke), C.byref(it)))
+        return mem, cent[:ke.value * dim].reshape(ke.value, dim), ke.value, it.value
 
     def cluster_assign(self, rows: np.ndarray, centroids: np.ndarray, empty: np.ndarray | None = None, with_distance: bool = True):
         """nearestCentroid of every host row over host centroids (yams_cluster_assign_device): (assign [n] uint32, distance
@@ -619,33 +608,19 @@ class Accel:
         tr = None if tie_rank is None else np.ascontiguousarray(tie_rank, dtype=np.uint32)
         sr = None if source_rows is None else np.ascontiguousarray(source_rows, dtype=np.uint32)
         S = n if sr is None else len(sr)
-        o_r = np.full((S, k), 0xffffffff, np.uint32); o_s = np.full((S, k), -np.inf, np.float32)
-        o_c = np.zeros(S, np.uint32); o_i = np.zeros(n, np.float32)
         flags = 0 if threshold is None else _lib.GRAPH_FLAG_EXPLICIT_THRESHOLD
         thr = 0.0 if threshold is None else threshold
         diag = _lib.GraphDiag()
-        if host_entry:
-            self._check(self.L.yams_graph_semantic_neighbors_host(
-                self.ctx, x.ctypes.data, n, dim, tr.ctypes.data if tr is not None else None, sr.ctypes.data if sr is not None else None, S,
-                k, flags, thr, o_r.ctypes.data, o_s.ctypes.data, o_c.ctypes.data, o_i.ctypes.data, C.byref(diag)))
-            return o_r, o_s, o_c, o_i, diag.as_dict()
-        bufs = [self.to_device(a) if a is not None and a.size else None for a in (x, tr, sr)]
-        d_x, d_t, d_s = bufs
-        outs = [self.alloc(S * k * 4 + 16), self.alloc(S * k * 4 + 16), self.alloc(S * 4 + 16), self.alloc(n * 4 + 16)]
-        try:
-            self._check(self.L.yams_graph_semantic_neighbors_device(
-                self.ctx, d_x.ptr if d_x else None, n, dim, d_t.ptr if d_t else None, d_s.ptr if d_s else None, S, k, flags, thr,
-                outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr, C.byref(diag)))
-            if k and n >= 2 and S:
-                o_r = outs[0].download(np.uint32, S * k).reshape(S, k)
-                o_s = outs[1].download(np.float32, S * k).reshape(S, k)
-                o_c = outs[2].download(np.uint32, S)
-                o_i = outs[3].download(np.float32, n)
-        finally:
-            for b in bufs + outs:
-                if b is not None:
-                    b.free()
-        return o_r, o_s, o_c, o_i, diag.as_dict()
+
+        def some(a):      # a list without entries still has to be an address: a null pointer means "every row" / "no ranks"
+            return None if a is None else (a if a.size else np.zeros(1, a.dtype))
+        o_r, o_s, o_c, o_i = self._artifact_call(
+            self.L.yams_graph_semantic_neighbors_device, self.L.yams_graph_semantic_neighbors_host, host_entry,
+            [x if x.size else None, some(tr), some(sr)], [(np.uint32, S * k), (np.float32, S * k), (np.uint32, S), (np.float32, n)],
+            lambda i, o: (i[0], n, dim, i[1], i[2], S, k, flags, thr, o[0], o[1], o[2], o[3], C.byref(diag)))
+        if not (k and n >= 2 and S):      # the entry writes nothing then: an empty result
+            o_r[:] = 0xffffffff; o_s[:] = -np.inf; o_c[:] = 0; o_i[:] = 0
+        return o_r.reshape(S, k), o_s.reshape(S, k), o_c, o_i, diag.as_dict()
 
     def semantic_neighbors_host(self, rows: np.ndarray, k: int = 8, **kw):
         """semantic_neighbors through yams_graph_semantic_neighbors_host (host arrays in, host arrays out)."""
@@ -671,24 +646,12 @@ class Accel:
         off = np.ascontiguousarray(row_offsets, dtype=np.uint64)
         c = np.ascontiguousarray(cols, dtype=np.uint32)
         w = np.ascontiguousarray(weights, dtype=np.float32)
-        out = np.zeros((n, dim), np.float32)
-        if host_entry:
-            diag = _lib.SgcDiag()
-            self._check(self.L.yams_graph_sgc_smooth_host(self.ctx, x.ctypes.data, n, dim, off.ctypes.data, c.ctypes.data if c.size else None,
-                                                          w.ctypes.data if w.size else None, hops, out.ctypes.data, C.byref(diag)))
-            return out, diag.as_dict()
-        bufs = [self.to_device(a) if a.size else None for a in (x, off, c, w)]
-        d_out = self.alloc(x.size * 4 + 16)
-        try:
-            diag = self.sgc_smooth_device(*(b.ptr if b else None for b in bufs[:1]), n, dim, *(b.ptr if b else None for b in bufs[1:]),
-                                          hops, d_out.ptr)
-            if x.size:
-                out = d_out.download(np.float32, x.size).reshape(n, dim)
-        finally:
-            for b in bufs + [d_out]:
-                if b is not None:
-                    b.free()
-        return out, diag
+        diag = _lib.SgcDiag()
+        out, = self._artifact_call(
+            self.L.yams_graph_sgc_smooth_device, self.L.yams_graph_sgc_smooth_host, host_entry,
+            [x if x.size else None, off, c if c.size else None, w if w.size else None], [(np.float32, x.size)],
+            lambda i, o: (i[0], n, dim, i[1], i[2], i[3], hops, o[0], C.byref(diag)))
+        return out.reshape(n, dim), diag.as_dict()
 
     # ---- cluster artifacts (yams_cluster_centroids / _representatives / _residuals) ----------------------------------------
     _GUARD = 0xA5

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 namespace yams_accel {
 
@@ -21,6 +22,20 @@ inline bool offsets_ascend(const uint64_t* off, uint64_t lists) {
     for (uint64_t i = 0; i < lists; ++i)
         if (off[i + 1] < off[i]) return false;
     return true;
+}
+
+// Is every idx[0 .. count) below `limit`?  An entry equal to `sentinel` is allowed when allow_sentinel says so ("none").
+inline bool indices_below(const uint32_t* idx, uint64_t count, uint64_t limit, bool allow_sentinel = false, uint32_t sentinel = 0xffffffffu) {
+    for (uint64_t i = 0; i < count; ++i)
+        if (idx[i] >= limit && !(allow_sentinel && idx[i] == sentinel)) return false;
+    return true;
+}
+
+// packed[i] = rows[select[i]], i < m, rows of `dim` floats: what a _host entry uploads when only the selected rows travel.
+// packed holds m * dim floats; every select[i] has been judged (indices_below) by the caller.
+inline void gather_rows(const float* rows, uint32_t dim, const uint32_t* select, uint64_t m, float* packed) {
+    for (uint64_t i = 0; i < m; ++i)
+        std::memcpy(packed + static_cast<size_t>(i) * dim, rows + static_cast<size_t>(select[i]) * dim, static_cast<size_t>(dim) * 4);
 }
 
 } // namespace yams_accel

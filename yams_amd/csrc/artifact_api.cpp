@@ -9,6 +9,7 @@
 #include "accel_ctx.h"
 #include "arg_checks.h"
 #include "artifact_launch.h"
+#include "host_stage.h"
 #include "kmeans_launch.h"
 
 using namespace yams_accel;
@@ -40,14 +41,6 @@ yams_status_t check_lists(yams_accel_ctx* ctx, const uint64_t* d_off, uint64_t l
     YA_TRY(read_words(ctx, d_flags, 1, &flags));
     if (flags & 1u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": the offsets do not start at 0 or decrease");
     if (flags & 2u) return fail(ctx, YAMS_ERR_INVALID_ARG, std::string(what) + ": an index is out of range");
-    return YAMS_OK;
-}
-
-// what the _host twins judge before they size an upload by the offsets
-yams_status_t host_offsets(yams_accel_ctx* ctx, const uint64_t* off, uint64_t lists, uint64_t* total) {
-    if (!offsets_ascend(off, lists)) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
-    *total = off[lists];
-    if (*total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
     return YAMS_OK;
 }
 
@@ -84,26 +77,23 @@ extern "C" yams_status_t yams_cluster_centroids_host(yams_accel_ctx* ctx, const 
     YA_TRY(check_shape(ctx, rows, n, dim, n_clusters));
     if (n_clusters == 0) return YAMS_OK;
     if (!cluster_offsets || !out_centroids || !out_counts) return fail(ctx, YAMS_ERR_INVALID_ARG, "null cluster_offsets or output");
-    uint64_t total;
-    YA_TRY(host_offsets(ctx, cluster_offsets, n_clusters, &total));
+    // judged here, before an upload is sized by them
+    if (!offsets_ascend(cluster_offsets, n_clusters)) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+    const uint64_t total = cluster_offsets[n_clusters];
+    if (total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
     if (total && !members) return fail(ctx, YAMS_ERR_INVALID_ARG, "null members");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t rb = static_cast<size_t>(n) * dim * 4, cb = static_cast<size_t>(n_clusters) * dim * 4;
-    float* d_rows; uint64_t* d_off; uint32_t* d_mem; float* d_cent; uint32_t* d_cnt;
-    YA_TRY(ws_get(ctx, "art_host_rows", rb + 16, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "art_host_offsets", (static_cast<size_t>(n_clusters) + 1) * 8, (void**)&d_off));
-    YA_TRY(ws_get(ctx, "art_host_list", static_cast<size_t>(total ? total : 1) * 4, (void**)&d_mem));
-    YA_TRY(ws_get(ctx, "art_host_centroids", cb, (void**)&d_cent));
-    YA_TRY(ws_get(ctx, "art_host_counts", static_cast<size_t>(n_clusters) * 4, (void**)&d_cnt));
-    if (rb) YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
-    YA_HIP(ctx, staged_h2d(d_off, cluster_offsets, (static_cast<size_t>(n_clusters) + 1) * 8, st));
-    if (total) YA_HIP(ctx, staged_h2d(d_mem, members, static_cast<size_t>(total) * 4, st));
+    HostStage hs(ctx);
+    const size_t c = n_clusters;
+    const float* d_rows = hs.up("art_host_rows", rows, static_cast<size_t>(n) * dim);
+    const uint64_t* d_off = hs.up("art_host_offsets", cluster_offsets, c + 1);
+    const uint32_t* d_mem = hs.up("art_host_list", members, static_cast<size_t>(total));
+    float* d_cent = hs.room<float>("art_host_centroids", c * dim);
+    uint32_t* d_cnt = hs.room<uint32_t>("art_host_counts", c);
+    YA_TRY(hs.status());
     YA_TRY(yams_cluster_centroids_device(ctx, d_rows, n, dim, d_off, d_mem, n_clusters, d_cent, d_cnt));
-    YA_HIP(ctx, hipMemcpyAsync(out_centroids, d_cent, cb, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipMemcpyAsync(out_counts, d_cnt, static_cast<size_t>(n_clusters) * 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out_centroids, d_cent, c * dim);
+    hs.down(out_counts, d_cnt, c);
+    return hs.finish();
 }
 
 // ---- representatives ------------------------------------------------------------------------------------------------------
@@ -170,33 +160,24 @@ extern "C" yams_status_t yams_cluster_representatives_host(yams_accel_ctx* ctx, 
     if (n_clusters == 0) return YAMS_OK;
     if (!cluster_offsets || !centroids || !out_counts || (n_extra && !out_selected))
         return fail(ctx, YAMS_ERR_INVALID_ARG, "null cluster_offsets, centroids or output");
-    uint64_t total;
-    YA_TRY(host_offsets(ctx, cluster_offsets, n_clusters, &total));
+    if (!offsets_ascend(cluster_offsets, n_clusters)) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+    const uint64_t total = cluster_offsets[n_clusters];
+    if (total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
     if (total && !candidates) return fail(ctx, YAMS_ERR_INVALID_ARG, "null candidates");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t rb = static_cast<size_t>(n) * dim * 4, cb = static_cast<size_t>(n_clusters) * dim * 4;
-    const size_t sb = static_cast<size_t>(n_clusters) * n_extra * 4;
-    float* d_rows; uint64_t* d_off; uint32_t* d_cand; float* d_cent; uint8_t* d_empty = nullptr; uint32_t* d_sel; uint32_t* d_cnt;
-    YA_TRY(ws_get(ctx, "art_host_rows", rb + 16, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "art_host_offsets", (static_cast<size_t>(n_clusters) + 1) * 8, (void**)&d_off));
-    YA_TRY(ws_get(ctx, "art_host_list", static_cast<size_t>(total ? total : 1) * 4, (void**)&d_cand));
-    YA_TRY(ws_get(ctx, "art_host_centroids", cb, (void**)&d_cent));
-    YA_TRY(ws_get(ctx, "art_host_selected", sb + 16, (void**)&d_sel));
-    YA_TRY(ws_get(ctx, "art_host_counts", static_cast<size_t>(n_clusters) * 4, (void**)&d_cnt));
-    if (centroid_empty) {
-        YA_TRY(ws_get(ctx, "art_host_empty", n_clusters, (void**)&d_empty));
-        YA_HIP(ctx, staged_h2d(d_empty, centroid_empty, n_clusters, st));
-    }
-    if (rb) YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
-    YA_HIP(ctx, staged_h2d(d_off, cluster_offsets, (static_cast<size_t>(n_clusters) + 1) * 8, st));
-    if (total) YA_HIP(ctx, staged_h2d(d_cand, candidates, static_cast<size_t>(total) * 4, st));
-    YA_HIP(ctx, staged_h2d(d_cent, centroids, cb, st));
+    HostStage hs(ctx);
+    const size_t c = n_clusters;
+    const float* d_rows = hs.up("art_host_rows", rows, static_cast<size_t>(n) * dim);
+    const uint64_t* d_off = hs.up("art_host_offsets", cluster_offsets, c + 1);
+    const uint32_t* d_cand = hs.up("art_host_list", candidates, static_cast<size_t>(total));
+    const float* d_cent = hs.up("art_host_centroids", centroids, c * dim);
+    const uint8_t* d_empty = hs.up("art_host_empty", centroid_empty, c);
+    uint32_t* d_sel = hs.room<uint32_t>("art_host_selected", c * n_extra);
+    uint32_t* d_cnt = hs.room<uint32_t>("art_host_counts", c);
+    YA_TRY(hs.status());
     YA_TRY(yams_cluster_representatives_device(ctx, d_rows, n, dim, d_off, d_cand, d_cent, d_empty, n_clusters, n_extra, d_sel, d_cnt));
-    if (sb) YA_HIP(ctx, hipMemcpyAsync(out_selected, d_sel, sb, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipMemcpyAsync(out_counts, d_cnt, static_cast<size_t>(n_clusters) * 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out_selected, d_sel, c * n_extra);
+    hs.down(out_counts, d_cnt, c);
+    return hs.finish();
 }
 
 // ---- residuals ------------------------------------------------------------------------------------------------------------
@@ -265,24 +246,18 @@ extern "C" yams_status_t yams_cluster_residuals_host(yams_accel_ctx* ctx, const 
                                out_cand_norm_sq, out_residual_dot));
     if (n == 0) return YAMS_OK;
     uint64_t total = 0;
-    if (cand_offsets) YA_TRY(host_offsets(ctx, cand_offsets, n, &total));
-    // judged here for the whole call, so that no slice is written before a later one is refused
-    for (uint64_t i = 0; primary && i < n; ++i)
-        if (primary[i] >= n_clusters && primary[i] != 0xffffffffu) return fail(ctx, YAMS_ERR_INVALID_ARG, "primary / cand: an index is out of range");
-    for (uint64_t i = 0; i < total; ++i)
-        if (cand[i] >= n_clusters) return fail(ctx, YAMS_ERR_INVALID_ARG, "primary / cand: an index is out of range");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t rb = static_cast<size_t>(n) * dim * 4, cb = static_cast<size_t>(n_clusters) * dim * 4;
-    float* d_rows; float* d_cent; uint32_t* d_pri = nullptr;
-    YA_TRY(ws_get(ctx, "art_host_rows", rb + 16, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "art_host_centroids", cb + 16, (void**)&d_cent));
-    YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
-    if (cb) YA_HIP(ctx, staged_h2d(d_cent, centroids, cb, st));
-    if (primary) {
-        YA_TRY(ws_get(ctx, "art_host_primary", static_cast<size_t>(n) * 4, (void**)&d_pri));
-        YA_HIP(ctx, staged_h2d(d_pri, primary, static_cast<size_t>(n) * 4, st));
+    if (cand_offsets) {
+        if (!offsets_ascend(cand_offsets, n)) return fail(ctx, YAMS_ERR_INVALID_ARG, "the offsets do not start at 0 or decrease");
+        total = cand_offsets[n];
+        if (total >= kMaxEntries) return fail(ctx, YAMS_ERR_UNSUPPORTED, "the lists must hold fewer than 2^32 entries");
     }
+    // judged here for the whole call, so that no slice is written before a later one is refused
+    if ((primary && !indices_below(primary, n, n_clusters, true)) || !indices_below(cand, total, n_clusters))
+        return fail(ctx, YAMS_ERR_INVALID_ARG, "primary / cand: an index is out of range");
+    HostStage hs(ctx);
+    const float* d_rows = hs.up("art_host_rows", rows, static_cast<size_t>(n) * dim);
+    const float* d_cent = hs.up("art_host_centroids", centroids, static_cast<size_t>(n_clusters) * dim);
+    const uint32_t* d_pri = hs.up("art_host_primary", primary, static_cast<size_t>(n));
     // slices of documents: [lo, hi) holds at most kHostOutBytes / 16 pairs (two fp64 outputs per pair), at least one document
     const uint64_t max_pairs = kHostOutBytes / 16;
     std::vector<uint64_t> local;
@@ -298,31 +273,28 @@ extern "C" yams_status_t yams_cluster_residuals_host(yams_accel_ctx* ctx, const 
             pairs = (hi - lo) * n_clusters;
         }
         const uint64_t m = hi - lo;
-        double* d_pn = nullptr; double* d_cn; double* d_rd = nullptr; uint64_t* d_off = nullptr; uint32_t* d_cand = nullptr;
-        const size_t p1 = static_cast<size_t>(pairs ? pairs : 1);
-        YA_TRY(ws_get(ctx, "art_host_cand_norm", p1 * 8, (void**)&d_cn));
-        if (primary) {
-            YA_TRY(ws_get(ctx, "art_host_primary_norm", static_cast<size_t>(m) * 8, (void**)&d_pn));
-            YA_TRY(ws_get(ctx, "art_host_residual_dot", p1 * 8, (void**)&d_rd));
-        }
+        const size_t np = static_cast<size_t>(pairs);
+        double* d_cn = hs.room<double>("art_host_cand_norm", np);
+        double* d_pn = primary ? hs.room<double>("art_host_primary_norm", static_cast<size_t>(m)) : nullptr;
+        double* d_rd = primary ? hs.room<double>("art_host_residual_dot", np) : nullptr;
+        const uint64_t* d_off = nullptr; const uint32_t* d_cand = nullptr;
         if (cand_offsets) {
             local.resize(m + 1);
             for (uint64_t i = 0; i <= m; ++i) local[i] = cand_offsets[lo + i] - cand_offsets[lo];
-            YA_TRY(ws_get(ctx, "art_host_offsets", static_cast<size_t>(m + 1) * 8, (void**)&d_off));
-            YA_TRY(ws_get(ctx, "art_host_list", p1 * 4, (void**)&d_cand));
-            YA_HIP(ctx, staged_h2d(d_off, local.data(), static_cast<size_t>(m + 1) * 8, st));
-            if (pairs) YA_HIP(ctx, staged_h2d(d_cand, cand + cand_offsets[lo], static_cast<size_t>(pairs) * 4, st));
-            YA_HIP(ctx, hipStreamSynchronize(st));      // `local` is reused by the next slice
+            d_off = hs.up("art_host_offsets", local.data(), static_cast<size_t>(m + 1));
+            d_cand = hs.up("art_host_list", cand + cand_offsets[lo], np);
+            YA_TRY(hs.finish());      // `local` is reused by the next slice
         }
+        YA_TRY(hs.status());
         const size_t o = static_cast<size_t>(cand_offsets ? cand_offsets[lo] : lo * n_clusters);
         YA_TRY(yams_cluster_residuals_device(ctx, d_rows + lo * dim, m, dim, d_cent, n_clusters, primary ? d_pri + lo : nullptr, d_off, d_cand,
                                              form, d_pn, d_cn, d_rd));
-        if (pairs) YA_HIP(ctx, hipMemcpyAsync(out_cand_norm_sq + o, d_cn, static_cast<size_t>(pairs) * 8, hipMemcpyDeviceToHost, st));
+        hs.down(out_cand_norm_sq + o, d_cn, np);
         if (primary) {
-            YA_HIP(ctx, hipMemcpyAsync(out_primary_norm_sq + lo, d_pn, static_cast<size_t>(m) * 8, hipMemcpyDeviceToHost, st));
-            if (pairs) YA_HIP(ctx, hipMemcpyAsync(out_residual_dot + o, d_rd, static_cast<size_t>(pairs) * 8, hipMemcpyDeviceToHost, st));
+            hs.down(out_primary_norm_sq + lo, d_pn, static_cast<size_t>(m));
+            hs.down(out_residual_dot + o, d_rd, np);
         }
-        YA_HIP(ctx, hipStreamSynchronize(st));
+        YA_TRY(hs.finish());
         lo = hi;
     }
     return YAMS_OK;

@@ -5,6 +5,7 @@
 #include "accel_ctx.h"
 #include "arg_checks.h"
 #include "embed_launch.h"
+#include "host_stage.h"
 
 using namespace yams_accel;
 
@@ -108,28 +109,28 @@ extern "C" yams_status_t yams_embed_pool_host(yams_accel_ctx* ctx, const float* 
     YA_TRY(check_pool(ctx, hidden, batch, seq, dim, mask, mask_len, mode, flags, out));
     if (batch == 0) return YAMS_OK;
     if (mask && mode == YAMS_EMBED_POOL_MEAN) YA_TRY(check_mask_host(ctx, mask, batch, mask_len, considered(seq, mask_len)));      // before an upload
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
+    HostStage hs(ctx);
     // CLS reads token 0 of every text and no mask: the copy is strided then
     const bool cls = mode == YAMS_EMBED_POOL_CLS;
-    if (cls) mask = nullptr;
     const uint32_t up_seq = cls ? 1u : seq;
-    const size_t hb = static_cast<size_t>(batch) * up_seq * dim * 4, mb = mask ? static_cast<size_t>(batch) * mask_len * 4 : 0,
-                 ob = static_cast<size_t>(batch) * dim * 4;
-    float* d_hidden; int32_t* d_mask = nullptr; float* d_out;
-    YA_TRY(ws_get(ctx, "embed_host_hidden", hb + 16, (void**)&d_hidden));
-    if (mb) YA_TRY(ws_get(ctx, "embed_host_mask", mb, (void**)&d_mask));
-    YA_TRY(ws_get(ctx, "embed_host_out", ob, (void**)&d_out));
-    if (cls && seq > 1)
-        YA_HIP(ctx, hipMemcpy2DAsync(d_hidden, static_cast<size_t>(dim) * 4, hidden, static_cast<size_t>(seq) * dim * 4, static_cast<size_t>(dim) * 4,
-                                     batch, hipMemcpyHostToDevice, st));
-    else
-        YA_HIP(ctx, staged_h2d(d_hidden, hidden, hb, st));
-    if (mb) YA_HIP(ctx, staged_h2d(d_mask, mask, mb, st));
+    const size_t rows = static_cast<size_t>(batch), row = static_cast<size_t>(dim);
+    const float* d_hidden;
+    if (cls && seq > 1) {      // not a plain copy: the room is HostStage's, the 2D copy stays here
+        float* d_cls = hs.room<float>("embed_host_hidden", rows * row);
+        if (d_cls) YA_HIP(ctx, hipMemcpy2DAsync(d_cls, row * 4, hidden, seq * row * 4, row * 4, rows, hipMemcpyHostToDevice, ctx->stream));
+        d_hidden = d_cls;
+    } else {
+        d_hidden = hs.up("embed_host_hidden", hidden, rows * up_seq * row);
+    }
+    // an empty mask (mask_len == 0) stays a NULL mask for the device twin, as a CLS call's does: a mask with an address is one
+    // the pooling kernels consult
+    const int32_t* d_mask = cls || !mask_len ? nullptr : hs.up("embed_host_mask", mask, rows * mask_len);
+    float* d_out = hs.room<float>("embed_host_out", rows * row);
+    YA_TRY(hs.status());
     yams_embed_diag_t dg{};
     YA_TRY(yams_embed_pool_device(ctx, d_hidden, batch, up_seq, dim, d_mask, mask_len, mode, flags, d_out, &dg));
-    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
+    hs.down(out, d_out, rows * row);
+    YA_TRY(hs.finish());
     if (diag) {
         dg.seq = seq;
         *diag = dg;
@@ -156,15 +157,12 @@ extern "C" yams_status_t yams_embed_normalize_host(yams_accel_ctx* ctx, const fl
     if (!ctx) return YAMS_ERR_INVALID_ARG;
     YA_TRY(check_normalize(ctx, rows, batch, dim, out));
     if (batch == 0) return YAMS_OK;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t rb = static_cast<size_t>(batch) * dim * 4;
-    float* d_rows; float* d_out;
-    YA_TRY(ws_get(ctx, "embed_host_hidden", rb + 16, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "embed_host_out", rb, (void**)&d_out));
-    YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
+    HostStage hs(ctx);
+    const size_t count = static_cast<size_t>(batch) * dim;
+    const float* d_rows = hs.up("embed_host_hidden", rows, count);
+    float* d_out = hs.room<float>("embed_host_out", count);
+    YA_TRY(hs.status());
     YA_TRY(yams_embed_normalize_device(ctx, d_rows, batch, dim, d_out));
-    YA_HIP(ctx, hipMemcpyAsync(out, d_out, rb, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out, d_out, count);
+    return hs.finish();
 }

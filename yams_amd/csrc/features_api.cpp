@@ -9,6 +9,7 @@
 #include "arg_checks.h"
 #include "artifact_launch.h"
 #include "features_launch.h"
+#include "host_stage.h"
 
 using namespace yams_accel;
 
@@ -137,23 +138,18 @@ extern "C" yams_status_t yams_features_aggregate_host(yams_accel_ctx* ctx, const
     if (!offsets_ascend(doc_offsets, n_docs)) return fail(ctx, YAMS_ERR_INVALID_ARG, "records: the offsets do not start at 0 or decrease");
     const uint64_t total = doc_offsets[n_docs];
     YA_TRY(check_aggregate_total(ctx, rows, n_records, dim, records, total, n_docs, out, out_counts));
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t rb = static_cast<size_t>(n_records) * dim * 4, ob = static_cast<size_t>(n_docs) * dim * 4;
-    float* d_rows; uint64_t* d_off; uint32_t* d_rec; float* d_out; uint32_t* d_cnt;
-    YA_TRY(ws_get(ctx, "feat_host_rows", rb + 16, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "feat_host_offsets", (static_cast<size_t>(n_docs) + 1) * 8, (void**)&d_off));
-    YA_TRY(ws_get(ctx, "feat_host_list", static_cast<size_t>(total ? total : 1) * 4, (void**)&d_rec));
-    YA_TRY(ws_get(ctx, "feat_host_out", ob, (void**)&d_out));
-    YA_TRY(ws_get(ctx, "feat_host_counts", static_cast<size_t>(n_docs) * 4, (void**)&d_cnt));
-    if (rb && rows) YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
-    YA_HIP(ctx, staged_h2d(d_off, doc_offsets, (static_cast<size_t>(n_docs) + 1) * 8, st));
-    if (total) YA_HIP(ctx, staged_h2d(d_rec, records, static_cast<size_t>(total) * 4, st));
+    HostStage hs(ctx);
+    const size_t nd = static_cast<size_t>(n_docs);
+    const float* d_rows = hs.up("feat_host_rows", rows, static_cast<size_t>(n_records) * dim);
+    const uint64_t* d_off = hs.up("feat_host_offsets", doc_offsets, nd + 1);
+    const uint32_t* d_rec = hs.up("feat_host_list", records, static_cast<size_t>(total));
+    float* d_out = hs.room<float>("feat_host_out", nd * dim);
+    uint32_t* d_cnt = hs.room<uint32_t>("feat_host_counts", nd);
+    YA_TRY(hs.status());
     YA_TRY(yams_features_aggregate_device(ctx, d_rows, n_records, dim, d_off, d_rec, n_docs, d_out, d_cnt));
-    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipMemcpyAsync(out_counts, d_cnt, static_cast<size_t>(n_docs) * 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out, d_out, nd * dim);
+    hs.down(out_counts, d_cnt, nd);
+    return hs.finish();
 }
 
 // ---- variance ----------------------------------------------------------------------------------------------------------------
@@ -183,30 +179,21 @@ extern "C" yams_status_t yams_features_variance_host(yams_accel_ctx* ctx, const 
     const uint64_t m = select ? n_select : n;
     YA_TRY(check_variance(ctx, rows, n, dim, m, form, out_mean, out_var));
     if (m == 0) return YAMS_OK;
-    for (uint64_t i = 0; select && i < m; ++i)
-        if (select[i] >= n) return fail(ctx, YAMS_ERR_INVALID_ARG, "select: an index is out of range");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
+    if (select && !indices_below(select, m, n)) return fail(ctx, YAMS_ERR_INVALID_ARG, "select: an index is out of range");
     // only the sample rows travel, packed in the order of the sums
     std::vector<float> packed;
-    const float* src = rows;
     if (select) {
         packed.resize(static_cast<size_t>(m) * dim);
-        for (uint64_t i = 0; i < m; ++i)
-            std::memcpy(packed.data() + static_cast<size_t>(i) * dim, rows + static_cast<size_t>(select[i]) * dim, static_cast<size_t>(dim) * 4);
-        src = packed.data();
+        gather_rows(rows, dim, select, m, packed.data());
     }
-    const size_t rb = static_cast<size_t>(m) * dim * 4;
-    float* d_rows; double* d_out;
-    YA_TRY(ws_get(ctx, "feat_host_rows", rb + 16, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "feat_host_moments", static_cast<size_t>(dim) * 16, (void**)&d_out));
-    YA_HIP(ctx, staged_h2d(d_rows, src, rb, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));      // `packed` goes away
+    HostStage hs(ctx);
+    const float* d_rows = hs.up("feat_host_rows", select ? packed.data() : rows, static_cast<size_t>(m) * dim);
+    double* d_out = hs.room<double>("feat_host_moments", static_cast<size_t>(dim) * 2);
+    YA_TRY(hs.finish());      // `packed` goes away
     YA_TRY(yams_features_variance_device(ctx, d_rows, m, dim, nullptr, 0, form, d_out, d_out + dim));
-    YA_HIP(ctx, hipMemcpyAsync(out_mean, d_out, static_cast<size_t>(dim) * 8, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipMemcpyAsync(out_var, d_out + dim, static_cast<size_t>(dim) * 8, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out_mean, d_out, dim);
+    hs.down(out_var, d_out + dim, dim);
+    return hs.finish();
 }
 
 // ---- compose -----------------------------------------------------------------------------------------------------------------
@@ -272,36 +259,25 @@ extern "C" yams_status_t yams_features_compose_host(yams_accel_ctx* ctx, const f
     ComposeShape sh;
     YA_TRY(check_compose(ctx, dense, n, dim, weights, entity, k, entity_on, sig, sig_len, sketch_on, sketch_dim, out, out_stride, out_dims, &sh));
     if (n == 0) return YAMS_OK;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
+    HostStage hs(ctx);
     const size_t nn = static_cast<size_t>(n);
-    const size_t db = nn * dim * 4, eb = nn * k * 4, sb = nn * sig_len * 4, ob = nn * out_stride * 4;
-    float* d_dense; float* d_ent = nullptr; uint8_t* d_eon = nullptr; uint32_t* d_sig = nullptr; uint8_t* d_son = nullptr; float* d_out; uint32_t* d_dims;
-    YA_TRY(ws_get(ctx, "feat_host_rows", db + 16, (void**)&d_dense));
-    YA_TRY(ws_get(ctx, "feat_host_out", ob + 16, (void**)&d_out));
-    YA_TRY(ws_get(ctx, "feat_host_counts", nn * 4, (void**)&d_dims));
-    YA_HIP(ctx, staged_h2d(d_dense, dense, db, st));
-    if (sh.entity) {
-        YA_TRY(ws_get(ctx, "feat_host_entity", eb, (void**)&d_ent));
-        YA_TRY(ws_get(ctx, "feat_host_entity_on", nn, (void**)&d_eon));
-        YA_HIP(ctx, staged_h2d(d_ent, entity, eb, st));
-        YA_HIP(ctx, staged_h2d(d_eon, entity_on, nn, st));
+    FeatComposeArgs a{};
+    a.dense = hs.up("feat_host_rows", dense, nn * dim); a.n = n; a.dim = dim;
+    a.k = k; a.sig_len = sig_len; a.sketch_dim = sketch_dim;
+    if (sh.entity) {      // a part that is off travels nowhere
+        a.entity = hs.up("feat_host_entity", entity, nn * k);
+        a.entity_on = hs.up("feat_host_entity_on", entity_on, nn);
     }
     if (sh.sketch) {
-        YA_TRY(ws_get(ctx, "feat_host_sig", sb, (void**)&d_sig));
-        YA_TRY(ws_get(ctx, "feat_host_sketch_on", nn, (void**)&d_son));
-        YA_HIP(ctx, staged_h2d(d_sig, sig, sb, st));
-        YA_HIP(ctx, staged_h2d(d_son, sketch_on, nn, st));
+        a.sig = hs.up("feat_host_sig", sig, nn * sig_len);
+        a.sketch_on = hs.up("feat_host_sketch_on", sketch_on, nn);
     }
-    FeatComposeArgs a{};
-    a.dense = d_dense; a.n = n; a.dim = dim;
-    a.entity = d_ent; a.k = k; a.entity_on = d_eon;
-    a.sig = d_sig; a.sig_len = sig_len; a.sketch_on = d_son; a.sketch_dim = sketch_dim;
     a.alpha_e = alpha_e; a.alpha_m = alpha_m;
-    a.out = d_out; a.out_stride = out_stride; a.out_dims = d_dims;
+    a.out = hs.room<float>("feat_host_out", nn * out_stride); a.out_stride = out_stride;
+    a.out_dims = hs.room<uint32_t>("feat_host_counts", nn);
+    YA_TRY(hs.status());
     YA_TRY(run_compose(ctx, sh, a));
-    if (ob) YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipMemcpyAsync(out_dims, d_dims, nn * 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out, a.out, nn * out_stride);
+    hs.down(out_dims, a.out_dims, nn);
+    return hs.finish();
 }

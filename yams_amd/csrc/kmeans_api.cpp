@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "host_stage.h"
 #include "kmeans_launch.h"
 
 using namespace yams_accel;
@@ -201,19 +202,16 @@ extern "C" yams_status_t yams_cluster_kmeans_host(yams_accel_ctx* ctx, const flo
     if (!out_membership) return fail(ctx, YAMS_ERR_INVALID_ARG, "null out_membership");
     const uint64_t k64 = effective_k(n, k);
     if (k64 > YAMS_CLUSTER_MAX_K) return fail(ctx, YAMS_ERR_UNSUPPORTED, "k exceeds YAMS_CLUSTER_MAX_K");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    float* d_rows; uint32_t* d_mem; float* d_cent = nullptr;
-    const size_t row_bytes = static_cast<size_t>(n) * dim * 4, cent_bytes = static_cast<size_t>(k64) * dim * 4;
-    YA_TRY(ws_get(ctx, "km_host_rows", row_bytes, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "km_host_membership", static_cast<size_t>(n) * 4, (void**)&d_mem));
-    if (out_centroids) YA_TRY(ws_get(ctx, "km_host_centroids", cent_bytes, (void**)&d_cent));
-    YA_HIP(ctx, staged_h2d(d_rows, rows, row_bytes, st));
+    HostStage hs(ctx);
+    const float* d_rows = hs.up("km_host_rows", rows, static_cast<size_t>(n) * dim);
+    uint32_t* d_mem = hs.room<uint32_t>("km_host_membership", static_cast<size_t>(n));
+    float* d_cent = out_centroids ? hs.room<float>("km_host_centroids", static_cast<size_t>(k64) * dim) : nullptr;
+    YA_TRY(hs.status());
     uint32_t ke = 0;
     YA_TRY(yams_cluster_kmeans_device(ctx, d_rows, n, dim, k, max_iterations, d_mem, d_cent, &ke, out_iterations));
-    YA_HIP(ctx, hipMemcpyAsync(out_membership, d_mem, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st));
-    if (out_centroids) YA_HIP(ctx, hipMemcpyAsync(out_centroids, d_cent, static_cast<size_t>(ke) * dim * 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
+    hs.down(out_membership, d_mem, static_cast<size_t>(n));
+    hs.down(out_centroids, d_cent, static_cast<size_t>(ke) * dim);
+    YA_TRY(hs.finish());
     if (out_k) *out_k = ke;
     return YAMS_OK;
 }

@@ -7,6 +7,8 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "arg_checks.h"
+#include "host_stage.h"
 #include "persistence_launch.h"
 
 using namespace yams_accel;
@@ -140,32 +142,23 @@ extern "C" yams_status_t yams_quality_persistence_h0_host(yams_accel_ctx* ctx, c
     Shape sh{};
     YA_TRY(check_args(ctx, rows, n, dim, select, n_select, form, out, &sh));
     const uint32_t m = sh.m;
-    for (uint32_t i = 0; select && i < m; ++i)
-        if (select[i] >= n) return fail(ctx, YAMS_ERR_INVALID_ARG, "a select entry is out of range");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
+    if (select && !indices_below(select, m, n)) return fail(ctx, YAMS_ERR_INVALID_ARG, "a select entry is out of range");
     // only the selected rows travel, packed in the order given
     std::vector<float> packed;
-    const float* src = rows;
     if (select && m) {
         packed.resize(static_cast<size_t>(m) * dim);
-        for (uint32_t i = 0; i < m; ++i) std::memcpy(packed.data() + static_cast<size_t>(i) * dim, rows + static_cast<size_t>(select[i]) * dim, static_cast<size_t>(dim) * 4);
-        src = packed.data();
+        gather_rows(rows, dim, select, m, packed.data());
     }
-    float* d_rows = nullptr;
-    const size_t rb = static_cast<size_t>(m) * dim * 4;
-    YA_TRY(ws_get(ctx, "persist_host_rows", rb + 16, (void**)&d_rows));
-    if (rb) {
-        YA_HIP(ctx, staged_h2d(d_rows, src, rb, st));
-        YA_HIP(ctx, hipStreamSynchronize(st));
-    }
+    HostStage hs(ctx);
+    const float* d_rows = hs.up("persist_host_rows", packed.empty() ? rows : packed.data(), static_cast<size_t>(m) * dim);
+    YA_TRY(m ? hs.finish() : hs.status());      // `packed` goes away (without points nothing was enqueued, and run() reads no row)
     yams_persistence_h0_t res{};
     std::vector<double> w;
     double* d_mat = nullptr;
     YA_TRY(run(ctx, d_rows, m, dim, nullptr, sh, form, &res, nullptr, &d_mat, w, out_stage_ms));
     if (out_distances && d_mat) {
-        YA_HIP(ctx, hipMemcpyAsync(out_distances, d_mat, static_cast<size_t>(m) * m * 8, hipMemcpyDeviceToHost, st));
-        YA_HIP(ctx, hipStreamSynchronize(st));
+        hs.down(out_distances, d_mat, static_cast<size_t>(m) * m);
+        YA_TRY(hs.finish());
     }
     if (out_merge_weights && !w.empty()) std::memcpy(out_merge_weights, w.data(), w.size() * 8);
     *out = res;

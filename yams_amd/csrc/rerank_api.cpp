@@ -7,6 +7,7 @@
 
 #include "accel_ctx.h"
 #include "arg_checks.h"
+#include "host_stage.h"
 #include "rerank_launch.h"
 
 using namespace yams_accel;
@@ -135,27 +136,22 @@ extern "C" yams_status_t yams_rerank_maxsim_host(yams_accel_ctx* ctx, const floa
     YA_TRY(check_offsets_host(ctx, doc_offsets, n_docs));      // judged here, before an upload is sized by them
     const uint64_t total = doc_offsets[n_docs];
     YA_TRY(check_maxsim_total(ctx, query, tq, dim, rows, total, n_docs, out_scores, out_rowmax));
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t rb = static_cast<size_t>(total) * dim * 4, qb = static_cast<size_t>(tq) * dim * 4, sb = static_cast<size_t>(n_docs) * 4,
-                 mb = static_cast<size_t>(n_docs) * tq * 4;
-    const bool want_max = out_rowmax && mb, want_arg = want_max && out_rowarg;
-    float* d_q; float* d_rows; uint64_t* d_off; float* d_scores; float* d_max = nullptr; uint32_t* d_arg = nullptr;
-    YA_TRY(ws_get(ctx, "rerank_host_query", qb + 16, (void**)&d_q));
-    YA_TRY(ws_get(ctx, "rerank_host_rows", rb + 16, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "rerank_host_offsets", (static_cast<size_t>(n_docs) + 1) * 8, (void**)&d_off));
-    YA_TRY(ws_get(ctx, "rerank_host_scores", sb, (void**)&d_scores));
-    if (want_max) YA_TRY(ws_get(ctx, "rerank_host_rowmax", mb, (void**)&d_max));
-    if (want_arg) YA_TRY(ws_get(ctx, "rerank_host_rowarg", mb, (void**)&d_arg));
-    if (qb) YA_HIP(ctx, staged_h2d(d_q, query, qb, st));
-    if (rb) YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
-    YA_HIP(ctx, staged_h2d(d_off, doc_offsets, (static_cast<size_t>(n_docs) + 1) * 8, st));
+    HostStage hs(ctx);
+    const size_t nd = static_cast<size_t>(n_docs), cells = nd * tq;
+    const bool want_max = out_rowmax && cells, want_arg = want_max && out_rowarg;
+    const float* d_q = hs.up("rerank_host_query", query, static_cast<size_t>(tq) * dim);
+    const float* d_rows = hs.up("rerank_host_rows", rows, static_cast<size_t>(total) * dim);
+    const uint64_t* d_off = hs.up("rerank_host_offsets", doc_offsets, nd + 1);
+    float* d_scores = hs.room<float>("rerank_host_scores", nd);
+    float* d_max = want_max ? hs.room<float>("rerank_host_rowmax", cells) : nullptr;
+    uint32_t* d_arg = want_arg ? hs.room<uint32_t>("rerank_host_rowarg", cells) : nullptr;
+    YA_TRY(hs.status());
     yams_rerank_diag_t dg{};
     YA_TRY(yams_rerank_maxsim_device(ctx, d_q, tq, dim, d_rows, d_off, n_docs, form, d_scores, d_max, d_arg, &dg));
-    YA_HIP(ctx, hipMemcpyAsync(out_scores, d_scores, sb, hipMemcpyDeviceToHost, st));
-    if (want_max) YA_HIP(ctx, hipMemcpyAsync(out_rowmax, d_max, mb, hipMemcpyDeviceToHost, st));
-    if (want_arg) YA_HIP(ctx, hipMemcpyAsync(out_rowarg, d_arg, mb, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
+    hs.down(out_scores, d_scores, nd);
+    if (want_max) hs.down(out_rowmax, d_max, cells);
+    if (want_arg) hs.down(out_rowarg, d_arg, cells);
+    YA_TRY(hs.finish());
     if (diag) *diag = dg;
     return YAMS_OK;
 }
@@ -189,17 +185,13 @@ extern "C" yams_status_t yams_rerank_maxpool_host(yams_accel_ctx* ctx, const flo
     YA_TRY(check_offsets_host(ctx, doc_offsets, n_docs));
     const uint64_t total = doc_offsets[n_docs];
     YA_TRY(check_maxpool_total(ctx, dim, rows, total, n_docs, out));
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t rb = static_cast<size_t>(total) * dim * 4, ob = static_cast<size_t>(n_docs) * dim * 4;
-    float* d_rows; uint64_t* d_off; float* d_out;
-    YA_TRY(ws_get(ctx, "rerank_host_rows", rb + 16, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "rerank_host_offsets", (static_cast<size_t>(n_docs) + 1) * 8, (void**)&d_off));
-    YA_TRY(ws_get(ctx, "rerank_host_pooled", ob, (void**)&d_out));
-    if (rb) YA_HIP(ctx, staged_h2d(d_rows, rows, rb, st));
-    YA_HIP(ctx, staged_h2d(d_off, doc_offsets, (static_cast<size_t>(n_docs) + 1) * 8, st));
+    HostStage hs(ctx);
+    const size_t nd = static_cast<size_t>(n_docs);
+    const float* d_rows = hs.up("rerank_host_rows", rows, static_cast<size_t>(total) * dim);
+    const uint64_t* d_off = hs.up("rerank_host_offsets", doc_offsets, nd + 1);
+    float* d_out = hs.room<float>("rerank_host_pooled", nd * dim);
+    YA_TRY(hs.status());
     YA_TRY(yams_rerank_maxpool_device(ctx, d_rows, dim, d_off, n_docs, d_out));
-    YA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out, d_out, nd * dim);
+    return hs.finish();
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "accel_ctx.h"
+#include "host_stage.h"
 #include "route_launch.h"
 
 using namespace yams_accel;
@@ -240,22 +241,17 @@ extern "C" yams_status_t yams_route_dense_host(yams_route_index* ix, const float
     YA_TRY(check_dense_args(ix, queries, nq, out_dense, out_observed, out_evals));
     if (diag) *diag = yams_route_diag_t{};
     if (nq == 0) return YAMS_OK;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
+    HostStage hs(ctx);
     const uint32_t c = ix->n_clusters, words = (c + 31) / 32;
-    const size_t c1 = c ? c : 1;
     // slices of queries whose outputs (dense, observed, evals) fit kHostOutBytes
-    const uint32_t per = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(nq, kHostOutBytes / (c1 * 5 + 4))));
-    float* d_q; uint32_t* d_cand = nullptr; float* d_dense; uint8_t* d_obs; uint32_t* d_evals;
-    YA_TRY(ws_get(ctx, "route_host_queries", static_cast<size_t>(nq) * ix->dim * 4, (void**)&d_q));
-    YA_TRY(ws_get(ctx, "route_host_dense", static_cast<size_t>(per) * c1 * 4, (void**)&d_dense));
-    YA_TRY(ws_get(ctx, "route_host_observed", static_cast<size_t>(per) * c1, (void**)&d_obs));
-    YA_TRY(ws_get(ctx, "route_host_evals", static_cast<size_t>(per) * 4, (void**)&d_evals));
-    YA_HIP(ctx, staged_h2d(d_q, queries, static_cast<size_t>(nq) * ix->dim * 4, st));
-    if (candidates && words) {
-        YA_TRY(ws_get(ctx, "route_host_candidates", static_cast<size_t>(nq) * words * 4, (void**)&d_cand));
-        YA_HIP(ctx, staged_h2d(d_cand, candidates, static_cast<size_t>(nq) * words * 4, st));
-    }
+    const uint32_t per = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(nq, kHostOutBytes / (static_cast<size_t>(c ? c : 1) * 5 + 4))));
+    const float* d_q = hs.up("route_host_queries", queries, static_cast<size_t>(nq) * ix->dim);
+    // (without clusters a candidate set has no words: it stays a null pointer, as it is for the device twin's callers)
+    const uint32_t* d_cand = words ? hs.up("route_host_candidates", candidates, static_cast<size_t>(nq) * words) : nullptr;
+    float* d_dense = hs.room<float>("route_host_dense", static_cast<size_t>(per) * c);
+    uint8_t* d_obs = hs.room<uint8_t>("route_host_observed", static_cast<size_t>(per) * c);
+    uint32_t* d_evals = hs.room<uint32_t>("route_host_evals", per);
+    YA_TRY(hs.status());
     for (uint32_t q0 = 0; q0 < nq; q0 += per) {
         const uint32_t m = std::min(per, nq - q0);
         yams_route_diag_t d{};
@@ -263,11 +259,11 @@ extern "C" yams_status_t yams_route_dense_host(yams_route_index* ix, const float
                                        d_cand ? d_cand + static_cast<size_t>(q0) * words : nullptr, d_dense, d_obs, d_evals, &d));
         if (diag) { diag->pairs += d.pairs; diag->slices += d.slices; diag->form = d.form; }
         if (c) {
-            YA_HIP(ctx, hipMemcpyAsync(out_dense + static_cast<size_t>(q0) * c, d_dense, static_cast<size_t>(m) * c * 4, hipMemcpyDeviceToHost, st));
-            YA_HIP(ctx, hipMemcpyAsync(out_observed + static_cast<size_t>(q0) * c, d_obs, static_cast<size_t>(m) * c, hipMemcpyDeviceToHost, st));
+            hs.down(out_dense + static_cast<size_t>(q0) * c, d_dense, static_cast<size_t>(m) * c);
+            hs.down(out_observed + static_cast<size_t>(q0) * c, d_obs, static_cast<size_t>(m) * c);
         }
-        YA_HIP(ctx, hipMemcpyAsync(out_evals + q0, d_evals, static_cast<size_t>(m) * 4, hipMemcpyDeviceToHost, st));
-        YA_HIP(ctx, hipStreamSynchronize(st));
+        hs.down(out_evals + q0, d_evals, m);
+        YA_TRY(hs.finish());
     }
     return YAMS_OK;
 }

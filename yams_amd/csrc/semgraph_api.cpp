@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "accel_ctx.h"
+#include "host_stage.h"
 #include "semgraph_launch.h"
 
 using namespace yams_accel;
@@ -104,25 +105,20 @@ extern "C" yams_status_t yams_graph_semantic_neighbors_host(yams_accel_ctx* ctx,
     bool done;
     YA_TRY(check_args(ctx, rows, n, dim, source_rows, n_sources, k, flags, threshold, out_rows, out_sims, out_counts, &S, &done));
     if (done) return YAMS_OK;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t row_bytes = static_cast<size_t>(n) * dim * 4, slots = static_cast<size_t>(S) * k;
-    float* d_rows; uint32_t* d_tie = nullptr; uint32_t* d_src = nullptr; uint32_t* d_or; float* d_os; uint32_t* d_oc; float* d_oi = nullptr;
-    YA_TRY(ws_get(ctx, "sg_host_rows", row_bytes, (void**)&d_rows));
-    if (tie_rank) YA_TRY(ws_get(ctx, "sg_host_tie", static_cast<size_t>(n) * 4, (void**)&d_tie));
-    if (source_rows) YA_TRY(ws_get(ctx, "sg_host_sources", static_cast<size_t>(S) * 4, (void**)&d_src));
-    YA_TRY(ws_get(ctx, "sg_host_out_rows", slots * 4, (void**)&d_or));
-    YA_TRY(ws_get(ctx, "sg_host_out_sims", slots * 4, (void**)&d_os));
-    YA_TRY(ws_get(ctx, "sg_host_out_counts", static_cast<size_t>(S) * 4, (void**)&d_oc));
-    if (out_inv_norm) YA_TRY(ws_get(ctx, "sg_host_out_inv", static_cast<size_t>(n) * 4, (void**)&d_oi));
-    YA_HIP(ctx, staged_h2d(d_rows, rows, row_bytes, st));
-    if (tie_rank) YA_HIP(ctx, staged_h2d(d_tie, tie_rank, static_cast<size_t>(n) * 4, st));
-    if (source_rows) YA_HIP(ctx, staged_h2d(d_src, source_rows, static_cast<size_t>(S) * 4, st));
+    HostStage hs(ctx);
+    const size_t nn = static_cast<size_t>(n), ns = static_cast<size_t>(S), slots = ns * k;
+    const float* d_rows = hs.up("sg_host_rows", rows, nn * dim);
+    const uint32_t* d_tie = hs.up("sg_host_tie", tie_rank, nn);
+    const uint32_t* d_src = hs.up("sg_host_sources", source_rows, ns);
+    uint32_t* d_or = hs.room<uint32_t>("sg_host_out_rows", slots);
+    float* d_os = hs.room<float>("sg_host_out_sims", slots);
+    uint32_t* d_oc = hs.room<uint32_t>("sg_host_out_counts", ns);
+    float* d_oi = out_inv_norm ? hs.room<float>("sg_host_out_inv", nn) : nullptr;
+    YA_TRY(hs.status());
     YA_TRY(yams_graph_semantic_neighbors_device(ctx, d_rows, n, dim, d_tie, d_src, S, k, flags, threshold, d_or, d_os, d_oc, d_oi, out_diag));
-    YA_HIP(ctx, hipMemcpyAsync(out_rows, d_or, slots * 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipMemcpyAsync(out_sims, d_os, slots * 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipMemcpyAsync(out_counts, d_oc, static_cast<size_t>(S) * 4, hipMemcpyDeviceToHost, st));
-    if (out_inv_norm) YA_HIP(ctx, hipMemcpyAsync(out_inv_norm, d_oi, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out_rows, d_or, slots);
+    hs.down(out_sims, d_os, slots);
+    hs.down(out_counts, d_oc, ns);
+    hs.down(out_inv_norm, d_oi, nn);
+    return hs.finish();
 }

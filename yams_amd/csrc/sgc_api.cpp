@@ -8,6 +8,7 @@
 
 #include "accel_ctx.h"
 #include "arg_checks.h"
+#include "host_stage.h"
 #include "sgc_launch.h"
 
 using namespace yams_accel;
@@ -117,22 +118,15 @@ extern "C" yams_status_t yams_graph_sgc_smooth_host(yams_accel_ctx* ctx, const f
     const uint64_t nnz = row_offsets[n];
     if (nnz >= (1ull << 32)) return fail(ctx, YAMS_ERR_UNSUPPORTED, "nnz must be < 2^32");
     if (nnz && (!cols || !weights)) return fail(ctx, YAMS_ERR_INVALID_ARG, "null cols or weights");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    float* d_rows; float* d_out; uint64_t* d_off; uint32_t* d_cols; float* d_w;
-    YA_TRY(ws_get(ctx, "sgc_host_rows", row_bytes, (void**)&d_rows));
-    YA_TRY(ws_get(ctx, "sgc_host_out", row_bytes, (void**)&d_out));
-    YA_TRY(ws_get(ctx, "sgc_host_offsets", static_cast<size_t>(n + 1) * 8, (void**)&d_off));
-    YA_TRY(ws_get(ctx, "sgc_host_cols", static_cast<size_t>(nnz ? nnz : 1) * 4, (void**)&d_cols));
-    YA_TRY(ws_get(ctx, "sgc_host_weights", static_cast<size_t>(nnz ? nnz : 1) * 4, (void**)&d_w));
-    YA_HIP(ctx, staged_h2d(d_rows, rows, row_bytes, st));
-    YA_HIP(ctx, staged_h2d(d_off, row_offsets, static_cast<size_t>(n + 1) * 8, st));
-    if (nnz) {
-        YA_HIP(ctx, staged_h2d(d_cols, cols, static_cast<size_t>(nnz) * 4, st));
-        YA_HIP(ctx, staged_h2d(d_w, weights, static_cast<size_t>(nnz) * 4, st));
-    }
+    HostStage hs(ctx);
+    const size_t cells = static_cast<size_t>(n) * dim;
+    const float* d_rows = hs.up("sgc_host_rows", rows, cells);
+    const uint64_t* d_off = hs.up("sgc_host_offsets", row_offsets, static_cast<size_t>(n) + 1);
+    const uint32_t* d_cols = hs.up("sgc_host_cols", cols, static_cast<size_t>(nnz));
+    const float* d_w = hs.up("sgc_host_weights", weights, static_cast<size_t>(nnz));
+    float* d_out = hs.room<float>("sgc_host_out", cells);
+    YA_TRY(hs.status());
     YA_TRY(yams_graph_sgc_smooth_device(ctx, d_rows, n, dim, d_off, d_cols, d_w, hops, d_out, out_diag));
-    YA_HIP(ctx, hipMemcpyAsync(out, d_out, row_bytes, hipMemcpyDeviceToHost, st));
-    YA_HIP(ctx, hipStreamSynchronize(st));
-    return YAMS_OK;
+    hs.down(out, d_out, cells);
+    return hs.finish();
 }
